@@ -9,7 +9,9 @@ A step = one batch (--batch, default 768) of synthetic 640x480 RGB-D frames thro
        feature reduce).
 Headline workload (`value`): BASELINE.json configs[1] — 640x480 frames, ViT-B/16 768-D tokens (14x14 patch grid), 256^3
 grid of 0.1 m cells, every pixel ingested (depth_sample_rate 1), "room" depth (camera random-walking inside an 8x3x6 m
-box).  The K timed steps are repeated (engine reset in between) and the MEDIAN repeat is reported.
+box).  A plain run sets up, warms up, times the K steps once and prints the line (`--dump-outputs DIR` also writes what the
+timed path computed, see dump_outputs).  With `--full` (or `--repeats R`) the K timed steps are repeated (engine reset in
+between) and the MEDIAN repeat is reported.
 `--precision bf16` times the opt-in fast mode instead (bf16 weights / activations / tokens, GEMMs through hipBLASLt); at the
 default precision that configuration is measured as the side key `value_bf16_encoder_library_gemms`.
 With N>1 ranks each rank ingests its own frame shard (weak scaling) and the per-rank maps are merged by one
@@ -17,7 +19,7 @@ RCCL reduce-scatter at the end of the timed region.  `--gpus N` without a torchr
 itself (python -m torch.distributed.run on 127.0.0.1) and exits non-zero when fewer than N GPUs are visible; under
 torchrun WORLD_SIZE must equal --gpus.
 
-Prints ONE JSON line (rank 0) carrying, beside the contract keys:
+Prints ONE JSON line (rank 0).  With `--full` (and the --no-* switches to trim it) the line carries, beside the contract keys:
   roofline        the whole bsc_ingest call priced per SURVEY.md §8(d): algorithmic bytes of the batch / WALL time of the call
                   followed by bsc_sync, alone (main stream + order stage + rgb chain on the side stream); the main-stream
                   HIP-event times ride as side keys; dominant kernel named.  Sub-blocks: `encoder` (bound mfma: the 16-bit
@@ -91,7 +93,15 @@ def parse():
     ap.add_argument("--batch", type=int, default=768,
                     help="frames per step (per rank).  Sweep on one MI355X, same box: 384: 20.5 k frames/s, 512: 21.0 k, 768: 21.7 k, "
                          "1024: 21.3 k, 1536: 21.3 k — the encoder's GEMMs run 6-8 %% faster per frame at M = 151 296 rows than at 75 648")
-    ap.add_argument("--repeats", type=int, default=5, help="repetitions of the K timed steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the K timed steps; the median is reported (default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: roofline / per-stage / encoder figures, the host-feed, other-precision, "
+                         "CPU-baseline, workload, exact-mode, localize and PMC legs (the --no-* switches trim them); off: the run "
+                         "sets up, warms up, times the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64, ~40 MB at the default shapes; fixed seeded samples of the larger arrays), e.g. bench_outputs")
     ap.add_argument("--precision", choices=["f32", "bf16"], default="f32",
                     help="encoder precision of the headline: f32 = the reference's (f32 weights, activations and tokens; dense "
                          "layers, attention and LayerNorm in-tree on the fp16 matrix cores with split operands), bf16 = the opt-in "
@@ -116,7 +126,10 @@ def parse():
     ap.add_argument("--no-workloads", action="store_true", help="skip the hall / iid workloads and the C3 leg")
     ap.add_argument("--no-exact", action="store_true", help="skip the reference-semantics (exact mode) leg")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc traffic passes of the isolated bsc_ingest call")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    return a
 
 
 def ingest_alg_bytes(F, N, g, D, tok_bytes, U, P_sampled=0):
@@ -227,6 +240,7 @@ class Pipeline:
         tok = self.enc(self.rgbs[s])
         e1.record()
         self.enc_events.append((e0, e1))
+        self.last_tokens = tok            # what --dump-outputs writes of the encoder (the graph's output buffer: no copy)
         self.eng.ingest(self.depths[s], self.rgbs[s], tok, self.Ts[s * self.batch:(s + 1) * self.batch])
 
     def run(self, lo, hi):
@@ -339,6 +353,60 @@ def stage_rooflines(p, iso, tok_bytes):
         if ms > 0:
             out[name] = {"ms_per_call": ms, "bytes_per_call": b, "GBs": b / ms / 1e6, "frac": b / ms / 1e6 / HBM_PEAK_GBS}
     return out
+
+
+def dump_outputs(p, d, token_rows=4096, voxels=8192, chunk=1 << 17, seed=1234):
+    """--dump-outputs DIR: what the timed path handed its caller after its last step, as DIR/<name>.npy in float32 / float64 (about
+    40 MB at the default shapes).  Samples are fixed and seeded; voxels are sampled in KEY order (not id order), so two builds of
+    the library that build the same map give the same files.
+      tokens_last_step_sample      (token_rows, D) f32   encoder output of the last step, rows frame * g * g + patch ...
+      tokens_last_step_rows        (token_rows,) f64     ... these rows
+      map_keys_sample              (voxels, 3) f64       voxel keys of the sample, ascending
+      map_features_sample          (voxels, D) f32       their feature rows (sum in mean mode, max in max mode)
+      map_count_sample / map_rgb_sample / map_weight_sample   their point counts, colours, weights
+      map_feature_sum              (D,) f64              feature rows summed over EVERY voxel of the map (key order)
+      map_summary                  (3,) f64              voxels, points counted over every voxel, sum of the weights
+      heightmap / heightmap_rgb    (gs, gs) f64, (gs, gs, 3) f32   the top-down map: max height of a cell (0 where no point
+                                   fell: the library reports -inf there), its colour
+      heightmap_occupied           (gs, gs) f32          1 where a point fell, 0 elsewhere
+    Every file is finite.
+    Returns {name: bytes}."""
+    os.makedirs(d, exist_ok=True)
+    rs = np.random.RandomState(seed)
+    eng, dev = p.eng, p.eng.device
+    files = {}
+    tok = p.last_tokens.reshape(-1, p.last_tokens.shape[-1])
+    ti = np.sort(rs.choice(tok.shape[0], min(token_rows, tok.shape[0]), replace=False))
+    files["tokens_last_step_sample"] = tok[torch.from_numpy(ti).to(tok.device)].float().cpu().numpy()
+    files["tokens_last_step_rows"] = ti.astype(np.float64)
+    pos, rgb, w = eng.export_rgb()
+    order = np.lexsort((pos[:, 2], pos[:, 1], pos[:, 0]))
+    vi = order[np.sort(rs.choice(len(pos), min(voxels, len(pos)), replace=False))]
+    acc, cnt = eng.dense_gather(torch.from_numpy(np.ascontiguousarray(pos[vi])).to(dev))
+    files["map_keys_sample"] = pos[vi].astype(np.float64)
+    files["map_features_sample"] = acc.cpu().numpy()
+    files["map_count_sample"] = cnt.cpu().numpy().astype(np.float64)
+    files["map_rgb_sample"] = rgb[vi].astype(np.float32)
+    files["map_weight_sample"] = w[vi].astype(np.float32)
+    fsum = torch.zeros(eng.cfg.token_dim, dtype=torch.float64, device=dev)
+    csum = 0
+    for lo in range(0, len(order), chunk):
+        acc, cnt = eng.dense_gather(torch.from_numpy(np.ascontiguousarray(pos[order[lo:lo + chunk]])).to(dev))
+        fsum += acc.sum(dim=0, dtype=torch.float64)
+        csum += int(cnt.sum(dtype=torch.int64).item())
+    del acc, cnt
+    files["map_feature_sum"] = fsum.cpu().numpy()
+    files["map_summary"] = np.array([len(pos), csum, w.astype(np.float64).sum()], np.float64)
+    mh, cv = eng.export_heightmap()
+    occ = np.isfinite(mh)
+    files["heightmap"] = np.where(occ, mh, 0.0).astype(np.float64)
+    files["heightmap_occupied"] = occ.astype(np.float32)
+    files["heightmap_rgb"] = cv.astype(np.float32)
+    bad = [name for name, arr in files.items() if not np.isfinite(arr).all()]
+    assert not bad, f"--dump-outputs: not finite: {bad}"
+    for name, arr in files.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
+    return {name: int(arr.nbytes) for name, arr in files.items()}
 
 
 def timed_repeats(q, w, n, repeats):
@@ -1065,10 +1133,11 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
         times.append(dt)
-        if rank == 0:
+        if rank == 0 and a.full:
             stage_timed = p.stage_ms()
             c1 = p.eng.counters()
     dt = statistics.median(times)
+    dumped = dump_outputs(p, a.dump_outputs) if rank == 0 and a.dump_outputs else None
 
     out = None
     if rank == 0:
@@ -1097,6 +1166,17 @@ def main():
         if dist_info:
             out["config"]["distributed"] = dist_info
             out["rccl_ranks"] = dist_info["ranks_counted_by_all_reduce"] if dist_info["is_rccl"] else 0
+        out["full"] = a.full
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "bytes": sum(dumped.values()), "files": sorted(dumped)}
+    if not a.full:                        # a plain run: the headline only
+        if rank == 0:
+            print(json.dumps(out))
+        if dist_active:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     def guarded(key, fn, into=None):
         """an optional leg: its result under `key`, or {"error": ...} — never the loss of the headline line"""
         tgt = out if into is None else into

@@ -1,6 +1,6 @@
 # A/B of environment knobs under the bench's isolated ingest leg: env_ab.sh "VAR=val" "VAR2=val" ...  (one box, alternating)
 for v in "" "$@" "" "$@"; do
-  env $v python bench.py --no-cpu-baseline --no-localize --no-workloads --no-exact --no-host-feed --no-side-precision --repeats 1 --steps 4 --warmup 2 2>/dev/null > /tmp/line.json
+  env $v python bench.py --full --no-cpu-baseline --no-localize --no-workloads --no-exact --no-host-feed --no-side-precision --repeats 1 --steps 4 --warmup 2 2>/dev/null > /tmp/line.json
   python - "[$v]" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/line.json").read()); r = d["roofline"]

@@ -1,6 +1,8 @@
 # per-kernel averages of the ingest kernels of one bench run (isolated ingest legs included)
+ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
+OUT="${OUT:-$ROOT/out}"                 # where the outputs go
 export TMPDIR=/tmp; rm -rf /tmp/ks; cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-localize --no-workloads --no-exact --no-host-feed --no-side-precision --repeats 1 --steps 3 --warmup 1 > /dev/null 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $ROOT/bench.py --full --no-cpu-baseline --no-localize --no-workloads --no-exact --no-host-feed --no-side-precision --repeats 1 --steps 3 --warmup 1 > /dev/null 2>&1
 f=$(find /tmp/ks -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'
 import csv, sys

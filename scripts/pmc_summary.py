@@ -62,7 +62,7 @@ if __name__ == "__main__":
     frames_per_call = int(sys.argv[4]) if len(sys.argv) > 4 else int(re.search(r'"--batch", type=int, default=(\d+)', _bench).group(1))
     d = summarise(os.path.join(root, "RD", "pmc_counter_collection.csv"), os.path.join(root, "WR", "pmc_counter_collection.csv"), frames_per_call, commit,
                   command="rocprofv3 --pmc <TCC_EA0_RDREQ TCC_EA0_RDREQ_32B TCC_EA0_RDREQ_64B TCC_EA0_RDREQ_128B | TCC_EA0_WRREQ TCC_EA0_WRREQ_64B> "
-                          "--kernel-trace -- python bench.py --no-cpu-baseline --no-localize --no-workloads --no-side-precision --no-host-feed --no-exact --no-pmc "
+                          "--kernel-trace -- python bench.py --full --no-cpu-baseline --no-localize --no-workloads --no-side-precision --no-host-feed --no-exact --no-pmc "
                           f"--repeats 1 (two separate passes; the default f32 pipeline, f32 tokens; 8 steps x {frames_per_call} frames, room depth), "
                           "or of scripts/ingest_only.py (bsc_ingest alone) when the tag says `only`",
                   token_bytes=int(os.environ.get("BSC_PMC_TOKEN_BYTES", "4")))
