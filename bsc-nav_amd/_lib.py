@@ -38,6 +38,7 @@ SIGNATURES = {
     "bsc_ingest": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, DRAW_FN, _VP]),
     "bsc_ingest_typed": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, DRAW_FN, _VP]),
     "bsc_flush": (_I32, [_VP, DRAW_FN, _VP]),
+    "bsc_flush_surprise": (_I32, [_VP, _I32, _F64, _F64]),
     "bsc_counters": (_I32, [_VP, _VP]),
     "bsc_geometry": (_I32, [_VP, _VP, _VP, _VP, _I64] + [_VP] * 8),
     "bsc_sort_pairs_u32": (_I32, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),
@@ -45,6 +46,7 @@ SIGNATURES = {
     "bsc_export_occupied": (_I32, [_VP, _VP]),
     "bsc_export_heightmap": (_I32, [_VP, _VP, _VP]),
     "bsc_export_cache": (_I32, [_VP, _VP, _VP, _VP]),
+    "bsc_import_cache": (_I32, [_VP, _I64, _VP, _VP, _VP]),
     "bsc_export_store": (_I32, [_VP, _VP, _VP, _VP, _VP]),
     "bsc_export_dense": (_I32, [_VP, _VP, _VP]),
     "bsc_import_rgb": (_I32, [_VP, _I64, _VP, _VP, _VP]),

@@ -61,6 +61,8 @@ struct RadixWs {
     uint32_t epoch;            // host counter: one value per (sort, pass)
 };
 
+struct SurpriseWs;   // surprise.hip: scratch of bsc_flush_surprise, allocated on its first call
+
 struct bsc_ctx {
     bsc_config c;
     int device;
@@ -172,6 +174,7 @@ struct bsc_ctx {
     int32_t *f_rowdst, *f_hit, *f_hidx, *f_rowseg, *f_rowe, *f_headpos, *f_win;
     uint32_t *f_draws;
     int64_t draws_cap;
+    SurpriseWs *surp;          // surprise flush scratch (nullptr until the first bsc_flush_surprise)
     // localize scratch
     float *l_sims;       // per token row / voxel row
     int64_t l_sims_cap, l_out_pos_cap, l_out_sim_cap;   // bytes
@@ -294,7 +297,11 @@ bsc_status ingest_batch(bsc_ctx *x, int32_t n_frames, const float *depth, const 
                         const void *tokens, int token_dtype, const int32_t *idx, const int64_t *offsets_host,
                         const double *alpha, bsc_draw_fn draw, void *user);
 bsc_status flush_cache(bsc_ctx *x, bsc_draw_fn draw, void *user);
-bsc_status grow_token_pool(bsc_ctx *x, int64_t need_rows);   // exact mode: the token store is unbounded like the reference's
+bsc_status grow_token_pool(bsc_ctx *x, int64_t need_rows);
+// update_memory_surp_base (surprise.hip): every iter_size row, tasks level by level; clears the cache like flush_cache
+bsc_status surprise_flush(bsc_ctx *x, int32_t radius, double surprise_threshold, double boring_threshold);
+bsc_status import_cache_impl(bsc_ctx *x, int64_t n_rows, const int32_t *pos_host, const float *feat_host, const float *dis_host);
+void surprise_ws_free(bsc_ctx *x);   // exact mode: the token store is unbounded like the reference's
 bsc_status launch_pending_chain(bsc_ctx *x);
 bsc_status launch_keys_pairs(bsc_ctx *x, int64_t P, int n_frames, bool all_pixels, const uint32_t *p_patf);
 bsc_status frontier_mask_impl(bsc_ctx *x, const uint8_t *navigable_host, uint8_t *mask_host);

@@ -369,6 +369,7 @@ extern "C" void bsc_destroy(bsc_ctx *x)
     hipSetDevice(x->device);
     if (x->side) hipStreamSynchronize(x->side);
     hipStreamSynchronize(x->stream);
+    surprise_ws_free(x);
     void *ptrs[] = {x->exp_tab, x->pat_x, x->pat_y, x->pt_rect, x->pt_off, x->occ, x->rgb_pos, x->rgb, x->weight, x->hmap, x->cv_map, x->dscal, x->cache_f, x->cache_pos,
                     x->cache_d, x->pool, x->pool_d, x->store_rows, x->store_cnt, x->acc, x->acnt, x->p_cell, x->p_patf,
                     x->p_rec_s[0], x->p_rec_s[1], x->p_r2f, x->new_cells, x->run_scan, x->seg_k0, x->seg_vid, x->blk_pass, x->blk_pass_off, x->hb_cnt, x->hb_off,
@@ -475,6 +476,14 @@ extern "C" bsc_status bsc_flush(bsc_ctx *x, bsc_draw_fn draw, void *user)
     if (x->c.mode != BSC_MODE_EXACT) { bsc_set_error("bsc_flush: only the exact mode has a token cache"); return BSC_E_STATE; }
     BSC_HIP(hipSetDevice(x->device));
     return flush_cache(x, draw, user);
+}
+
+extern "C" bsc_status bsc_flush_surprise(bsc_ctx *x, int32_t neighbor_radius, double surprise_threshold, double boring_threshold)
+{
+    if (!x) return BSC_E_INVALID;
+    if (x->c.mode != BSC_MODE_EXACT) { bsc_set_error("bsc_flush_surprise: only the exact mode has a token cache"); return BSC_E_STATE; }
+    BSC_HIP(hipSetDevice(x->device));
+    return surprise_flush(x, neighbor_radius, surprise_threshold, boring_threshold);
 }
 
 __global__ __launch_bounds__(TPB) void k_store_totals(int n, const int32_t *__restrict__ cnt, int64_t *out2)
@@ -652,6 +661,13 @@ extern "C" bsc_status bsc_export_cache(bsc_ctx *x, float *feat, int32_t *pos, fl
     if (pos) BSC_HIP(hipMemcpy(pos, x->cache_pos, sizeof(int32_t) * 3 * n, hipMemcpyDeviceToHost));
     if (dis) BSC_HIP(hipMemcpy(dis, x->cache_d, sizeof(float) * n, hipMemcpyDeviceToHost));
     return BSC_OK;
+}
+
+extern "C" bsc_status bsc_import_cache(bsc_ctx *x, int64_t n_rows, const int32_t *pos, const float *feat, const float *dis)
+{
+    if (!x || x->c.mode != BSC_MODE_EXACT) { bsc_set_error("bsc_import_cache: exact mode only"); return BSC_E_STATE; }
+    BSC_HIP(hipSetDevice(x->device));
+    return import_cache_impl(x, n_rows, pos, feat, dis);
 }
 
 // name key on the host (same encoding as localize.hip)

@@ -132,6 +132,10 @@ class VoxelEngine:
     def flush(self):
         _lib.check(self.lib.bsc_flush(self.h, self._draw, None))
 
+    def flush_surprise(self, radius=1, surprise_threshold=0.5, boring_threshold=0.95):
+        """update_memory_surp_base (memory_2.py:364-536) over every cache row; exact mode only."""
+        _lib.check(self.lib.bsc_flush_surprise(self.h, int(radius), float(surprise_threshold), float(boring_threshold)))
+
     def counters(self):
         out = np.zeros(10, np.int64)
         _lib.check(self.lib.bsc_counters(self.h, _hp(out)))
@@ -206,6 +210,13 @@ class VoxelEngine:
         feats = np.ascontiguousarray(feats, np.float32)
         dists = np.ascontiguousarray(dists, np.float32)
         _lib.check(self.lib.bsc_import_store(self.h, len(pos), len(feats), _hp(pos), _hp(cnt), _hp(feats), _hp(dists)))
+
+    def import_cache(self, pos, feat, dis):
+        """Counterpart of export_cache: rows 0 .. n-1 of the token cache (every cell must hold a voxel, [0,0,0] excepted)."""
+        pos = np.ascontiguousarray(pos, np.int32).reshape(-1, 3)
+        feat = np.ascontiguousarray(feat, np.float32).reshape(len(pos), self.cfg.token_dim)
+        dis = np.ascontiguousarray(dis, np.float32).reshape(len(pos))
+        _lib.check(self.lib.bsc_import_cache(self.h, len(pos), _hp(pos), _hp(feat), _hp(dis)))
 
     def import_dense(self, acc, cnt):
         acc = np.ascontiguousarray(acc, np.float32)

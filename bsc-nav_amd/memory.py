@@ -75,6 +75,9 @@ class VoxelTokenMemory:
         self.min_depth, self.max_depth = c.min_depth, c.max_depth
         self.token_dim = int(token_dim or c.token_dim)
         self.iter_size, self.cache_size = c.iter_size, c.cache_size
+        self.neighbor_radius = 1                                               # memory_2.py:113-115 (update_memory_surp_base)
+        self.boring_threshold = 0.95
+        self.surprise_threshold = 0.5
         self.camera_height = c.sensor_height
         self.floor_height, self.map_height = c.floor_height, c.map_height
         self.maxh = int(self.map_height / self.cs)                             # memory_2.py:122-123
@@ -185,6 +188,14 @@ class VoxelTokenMemory:
         """memory_2.py:326-358 — flush ALL iter_size cache rows into the per-voxel token store."""
         t1 = time.time()
         self.engine.flush()
+        self._touch()
+        self._log(f"finish updating, time:{time.time() - t1}")
+
+    def update_memory_surp_base(self):
+        """memory_2.py:364-536 — flush ALL iter_size cache rows by surprise against the neighbouring groups, then merge
+        each changed group by similarity; reads neighbor_radius / surprise_threshold / boring_threshold at call time."""
+        t1 = time.time()
+        self.engine.flush_surprise(self.neighbor_radius, self.surprise_threshold, self.boring_threshold)
         self._touch()
         self._log(f"finish updating, time:{time.time() - t1}")
 

@@ -99,6 +99,16 @@ bsc_status bsc_ingest_typed(bsc_ctx *ctx, int32_t n_frames, const float *depth_d
 /* update_memory_dist_base (memory_2.py:326-358): all iter_size rows incl. the zero rows. */
 bsc_status bsc_flush(bsc_ctx *ctx, bsc_draw_fn draw, void *user);
 
+/* update_memory_surp_base (memory_2.py:364-536; neighbor_radius, boring_threshold, surprise_threshold: :113-115): every
+ * iter_size row incl. the zero rows, in order: a missing group is created (:471-478); otherwise the row's surprise
+ * min(1 - cos) against the tokens of the existing groups within Chebyshev distance neighbor_radius (the voxel excluded,
+ * NaN propagating, +inf without any) is compared with surprise_threshold (:480-500); a surprising token is appended or
+ * overwrites the slot of the smallest 1 - cos (:448-468), then the group is merged by the components of
+ * sim > boring_threshold (:386-446).  The cache is cleared as by bsc_flush; no draws.  Exact mode only (BSC_E_STATE);
+ * BSC_E_INVALID for neighbor_radius outside [0, 3], a NaN threshold, cache_size > 64, or a radius whose
+ * ((2r+1)^3 - 1) x cache_size neighbour tokens (8 bytes each) plus one token exceed 48 KiB of LDS. */
+bsc_status bsc_flush_surprise(bsc_ctx *ctx, int32_t neighbor_radius, double surprise_threshold, double boring_threshold);
+
 /* counters (host sync): out[0]=max_id out[1]=iter_id out[2]=store voxels out[3]=store tokens
  * out[4]=flushes out[5]=points passed so far out[6]=points seen so far out[7]=voxel-row RMWs (dense)
  * out[8]=(voxel,frame,patch) pairs reduced so far (dense) out[9]=pairs of the last call */
@@ -122,6 +132,9 @@ bsc_status bsc_export_rgb(bsc_ctx *ctx, int32_t *pos_host, uint8_t *rgb_host, fl
 bsc_status bsc_export_occupied(bsc_ctx *ctx, int32_t *occ_host /* (gs,gs,max_h-min_h) */);
 bsc_status bsc_export_heightmap(bsc_ctx *ctx, double *max_height_host, uint8_t *cv_map_host);
 bsc_status bsc_export_cache(bsc_ctx *ctx, float *feat_host, int32_t *pos_host, float *dis_host);
+/* counterpart of bsc_export_cache (grid_feat / grid_feat_pos / grid_feat_dis, memory_2.py:708-713): rows 0 .. n_rows-1,
+ * iter_id = n_rows, the other rows zero.  BSC_E_INVALID (nothing changed) when a row's cell has no voxel, [0,0,0] excepted. */
+bsc_status bsc_import_cache(bsc_ctx *ctx, int64_t n_rows, const int32_t *pos_host, const float *feat_host, const float *dis_host);
 /* feature store in HDF5 name order: pos (V,3), cnt (V), feats (T,D), dists (T)  (feat.h5df, memory_2.py:330-354) */
 bsc_status bsc_export_store(bsc_ctx *ctx, int32_t *pos_host, int32_t *cnt_host, float *feats_host, float *dists_host);
 /* dense modes: accumulator rows in voxel-id order: acc (max_id,D) sum-or-max, cnt (max_id) */
