@@ -25,6 +25,12 @@ class BscConfig(C.Structure):
     ]
 
 
+class BscRegion(C.Structure):
+    """struct bsc_region: the sphere and floor band of one query of bsc_localize_regions (32 bytes, no padding)."""
+    _fields_ = [("radius", C.c_double), ("curr", C.c_int32 * 3), ("floor_lo", C.c_int32), ("floor_hi", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 DRAW_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32))
 
 # every symbol include/bscnav.h declares: name -> (restype, argtypes)
@@ -54,6 +60,7 @@ SIGNATURES = {
     "bsc_import_dense": (_I32, [_VP, _I64, _VP, _VP]),
     "bsc_pool_query": (_I32, [_VP, _VP, _I32, _I32, _I32, _VP]),
     "bsc_localize": (_I32, [_VP, _VP, _I32, _I32, _F64, _VP, _I32, _I32, _VP, _VP, _VP]),
+    "bsc_localize_regions": (_I32, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "bsc_cluster_centers": (_I32, [_VP, _I32, _I32, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
     "bsc_frontier_mask": (_I32, [_VP, _VP, _VP]),
     "bsc_frontier_clusters": (_I32, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

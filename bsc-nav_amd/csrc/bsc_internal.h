@@ -16,7 +16,7 @@ struct PointRec {
 // timed stages (bsc_kernel_stats `which`)
 enum {
     BSC_STAT_DENSE = 0,    // k_dense_reduce
-    BSC_STAT_COSINE = 1,   // cosine scan of bsc_localize
+    BSC_STAT_COSINE = 1,   // cosine scan of bsc_localize / bsc_localize_regions (bytes: the rows actually streamed)
     BSC_STAT_POINTS = 2,   // k_points
     BSC_STAT_PAIRS = 3,    // k_keys_pairs + tile scan + k_pair_compact
     BSC_STAT_ORDER = 4,    // new-voxel ids, k_runs, run sort, scan, k_expand, segment order (everything the rgb chain needs)
@@ -62,6 +62,7 @@ struct RadixWs {
 };
 
 struct SurpriseWs;   // surprise.hip: scratch of bsc_flush_surprise, allocated on its first call
+struct RegionWs;     // localize.hip: scratch of bsc_localize_regions, allocated on its first call
 
 struct bsc_ctx {
     bsc_config c;
@@ -199,7 +200,8 @@ struct bsc_ctx {
     bool row_scale_dirty;
     bool rscale_from_reduce;        // the last ingest's dense reduce wrote the scale / inverse norm of every row it finished
                                     // (k_dense_reduce_voxels): the scan's k_row_scale pass is then only needed after imports
-    int last_nq, last_K;            // shape of the last bsc_localize call (its top-K stays resident for clustering)
+    int last_nq, last_K;            // shape of the last bsc_localize / bsc_localize_regions call (its top-K stays resident for clustering)
+    RegionWs *regn;                 // bsc_localize_regions scratch (nullptr until its first call)
     int32_t last_counts[1024];
     // frontier helpers (allocated on first use, gs*gs each)
     uint8_t *fr_mask, *fr_in;
@@ -315,6 +317,9 @@ bsc_status dense_reduce_batch(bsc_ctx *x, const void *tokens, int token_dtype, i
 bsc_status compact_heads_u64(bsc_ctx *x, const u64 *keys, int64_t n, int shift, int32_t *out, int64_t *count_dev);
 bsc_status localize_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, double radius, const int32_t *curr,
                          int32_t floor_lo, int32_t floor_hi, int32_t *out_pos, float *out_sim, int32_t *out_count);
+bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, const bsc_region *regions,
+                                 int32_t *out_pos, float *out_sim, int32_t *out_count);
+void region_ws_free(bsc_ctx *x);
 int64_t sims_row_stride(int64_t n_rows);
 bsc_status pool_query_impl(bsc_ctx *x, const float *tokens, int32_t B, int32_t T, int32_t D, float *out);
 bsc_status read_scalars(bsc_ctx *x); // dscal -> hscal (synchronises the main stream)

@@ -370,6 +370,7 @@ extern "C" void bsc_destroy(bsc_ctx *x)
     if (x->side) hipStreamSynchronize(x->side);
     hipStreamSynchronize(x->stream);
     surprise_ws_free(x);
+    region_ws_free(x);
     void *ptrs[] = {x->exp_tab, x->pat_x, x->pat_y, x->pt_rect, x->pt_off, x->occ, x->rgb_pos, x->rgb, x->weight, x->hmap, x->cv_map, x->dscal, x->cache_f, x->cache_pos,
                     x->cache_d, x->pool, x->pool_d, x->store_rows, x->store_cnt, x->acc, x->acnt, x->p_cell, x->p_patf,
                     x->p_rec_s[0], x->p_rec_s[1], x->p_r2f, x->new_cells, x->run_scan, x->seg_k0, x->seg_vid, x->blk_pass, x->blk_pass_off, x->hb_cnt, x->hb_off,
@@ -1050,6 +1051,40 @@ extern "C" bsc_status bsc_localize(bsc_ctx *x, const float *q_dev, int32_t nq, i
     BSC_TRY(grow::run((void **)&x->l_out_pos, &x->l_out_pos_cap, (int64_t)nq * K * 12));
     BSC_TRY(grow::run((void **)&x->l_out_sim, &x->l_out_sim_cap, (int64_t)nq * K * 4));
     return localize_impl(x, q_dev, nq, K, radius, curr_host, floor_lo, floor_hi, out_pos_host, out_sim_host, out_count_host);
+}
+
+extern "C" bsc_status bsc_localize_regions(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, const bsc_region *regions_host,
+                                           int32_t *out_pos_host, float *out_sim_host, int32_t *out_count_host)
+{
+    if (!x || !q_dev || !out_pos_host || !out_sim_host || !out_count_host) return BSC_E_INVALID;
+    if (!regions_host) { bsc_set_error("bsc_localize_regions: regions_host is NULL"); return BSC_E_INVALID; }
+    if (K > 4096 || K < 1 || nq < 1 || nq > 1024) {
+        bsc_set_error("bsc_localize_regions: K=%d (1..4096), n_queries=%d (1..1024)", K, nq);
+        return BSC_E_INVALID;
+    }
+    for (int32_t i = 0; i < nq; ++i) {
+        if (regions_host[i].radius != regions_host[i].radius || regions_host[i].reserved != 0) {
+            bsc_set_error("bsc_localize_regions: region %d: radius is NaN or reserved != 0", i);
+            return BSC_E_INVALID;
+        }
+    }
+    BSC_HIP(hipSetDevice(x->device));
+    BSC_TRY(read_scalars(x));
+    const int64_t n_rows = x->c.mode == BSC_MODE_EXACT ? x->hscal[DS_POOL_N] : x->hscal[DS_MAX_ID];
+    const int64_t need = (int64_t)nq * sims_row_stride(n_rows > 0 ? n_rows : 1);
+    struct grow { static bsc_status run(void **p, int64_t *cap, int64_t need_bytes) {
+        if (*cap >= need_bytes) return BSC_OK;
+        if (*p) hipFree(*p);
+        *p = nullptr; *cap = 0;
+        hipError_t e = hipMalloc(p, (size_t)need_bytes);
+        if (e != hipSuccess) { bsc_set_error("bsc_localize_regions scratch: %s", hipGetErrorString(e)); return BSC_E_HIP; }
+        *cap = need_bytes;
+        return BSC_OK;
+    } };
+    BSC_TRY(grow::run((void **)&x->l_sims, &x->l_sims_cap, need * 4));
+    BSC_TRY(grow::run((void **)&x->l_out_pos, &x->l_out_pos_cap, (int64_t)nq * K * 12));
+    BSC_TRY(grow::run((void **)&x->l_out_sim, &x->l_out_sim_cap, (int64_t)nq * K * 4));
+    return localize_regions_impl(x, q_dev, nq, K, regions_host, out_pos_host, out_sim_host, out_count_host);
 }
 
 // ---- multi-GPU merge helpers (dense modes) ---------------------------------------------------------------

@@ -21,6 +21,49 @@ def _dp(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+REGION_DTYPE = np.dtype([("radius", np.float64), ("curr", np.int32, (3,)), ("floor_lo", np.int32), ("floor_hi", np.int32),
+                         ("reserved", np.int32)])          # struct bsc_region
+assert REGION_DTYPE.itemsize == C.sizeof(_lib.BscRegion) == 32
+
+
+def region_array(Q, radius=None, curr=None, floor=None):
+    """The (Q,) bsc_region array of VoxelEngine.localize_regions from its arguments (needs no context):
+    radius  None (no sphere for anyone), one number for all, or a sequence of Q numbers / Nones (None and inf: no sphere);
+    curr    (3,) for all or (Q,3); may be None only when no query has a sphere;
+    floor   None (no band for anyone), one (lo, hi) pair for all, or a sequence of Q pairs / Nones.
+    A sequence of the wrong length raises ValueError."""
+    Q = int(Q)
+    out = np.zeros(Q, REGION_DTYPE)
+    if radius is None or np.isscalar(radius):
+        radius = [radius] * Q
+    radius = list(radius)
+    if len(radius) != Q:
+        raise ValueError(f"radius: {len(radius)} entries for {Q} queries")
+    out["radius"] = [-1.0 if (r is None or r == np.inf) else float(r) for r in radius]
+    if curr is None:
+        if np.any(~(out["radius"] < 0)):
+            raise ValueError("a sphere (radius) needs curr")
+    else:
+        c = np.asarray(curr)
+        if c.shape == (3,):
+            c = np.broadcast_to(c, (Q, 3))
+        if c.shape != (Q, 3):
+            raise ValueError(f"curr: shape {c.shape}, expected (3,) or ({Q}, 3)")
+        out["curr"] = c.astype(np.int32)
+    if floor is None:
+        floor = [None] * Q
+    elif len(floor) == 2 and all(np.isscalar(v) for v in floor):
+        floor = [floor] * Q
+    floor = list(floor)
+    if len(floor) != Q:
+        raise ValueError(f"floor: {len(floor)} entries for {Q} queries")
+    for i, f in enumerate(floor):
+        if f is not None and len(f) != 2:
+            raise ValueError(f"floor[{i}]: expected (lo, hi) or None")
+        out["floor_lo"][i], out["floor_hi"][i] = (0, -1) if f is None else (int(f[0]), int(f[1]))
+    return out
+
+
 class VoxelEngine:
     def __init__(self, height, width, grid_size, cell_size, floor_height, map_height, patch_grid, token_dim,
                  mode="exact", iter_size=50000, cache_size=10, voxel_capacity=None, token_capacity=None,
@@ -245,6 +288,19 @@ class VoxelEngine:
         self._enter(q)
         _lib.check(self.lib.bsc_localize(self.h, _dp(q), Q, K, -1.0 if radius is None else float(radius), _hp(curr_a),
                                          lo, hi, _hp(pos), _hp(sim), _hp(cnt)))
+        return pos, sim, cnt
+
+    def localize_regions(self, q, K=100, radius=None, curr=None, floor=None):
+        """localize with a sphere and a floor band per query, in one call (bsc_localize_regions): q (Q,D) f32 CUDA;
+        radius a sequence of Q floats / Nones or one value for all; curr (Q,3) or (3,); floor a sequence of (lo, hi) / None
+        or one (lo, hi) for all -> the triple of localize.  Only the rows some query can see are scanned when they are few."""
+        q = q.reshape(-1, self.cfg.token_dim).contiguous()
+        assert q.is_cuda and q.dtype == torch.float32
+        Q = q.shape[0]
+        regions = region_array(Q, radius, curr, floor)
+        pos, sim, cnt = np.zeros((Q, K, 3), np.int32), np.zeros((Q, K), np.float32), np.zeros(Q, np.int32)
+        self._enter(q)
+        _lib.check(self.lib.bsc_localize_regions(self.h, _dp(q), Q, K, _hp(regions), _hp(pos), _hp(sim), _hp(cnt)))
         return pos, sim, cnt
 
     def cluster_centers(self, pos=None, sim=None, K=None, query_index=0, eps=10.0, min_samples=5):

@@ -364,6 +364,34 @@ class VoxelTokenMemory:
         self._log(f"finish localizing, time:{time.time() - t1}")
         return np.array([top_pos[0]]), top_pos, top_sim
 
+    def voxel_localized_batch(self, prompts, K=100, region_radius=np.inf, curr_grid=None, floors=None):
+        """voxel_localized for several prompts in one call, each inside its own region (the adaptive-region loop of
+        BSCAgent.py:1078-1098, the augmented prompts of working_memory_retrival, one position per agent of a shared map).
+        prompts        list of whatever voxel_localized accepts, or a (Q,D) tensor of pooled embeddings;
+        region_radius  one value for all or one per prompt (np.inf / None: no sphere);
+        curr_grid      (3,) for all or (Q,3);
+        floors         None: the loaded single floor for every query exactly when voxel_localized applies it
+                       (args.load_single_floor); a list of (lo, hi) / None per prompt overrides it.
+        -> list of (top1 (1,3), positions (n,3) int64, similarities (n,) float64), one per prompt.  Unlike voxel_localized,
+        which raises IndexError like the reference, a prompt whose region holds no voxel gives empty arrays and a top1 of
+        shape (0,3): one empty region must not lose the other answers."""
+        t1 = time.time()
+        if isinstance(prompts, torch.Tensor) and prompts.dim() == 2:
+            q = prompts.to(self.device, torch.float32).contiguous()
+        else:
+            q = torch.cat([self._query_embedding(p) for p in prompts], 0)
+        Q = q.shape[0]
+        if floors is None and getattr(self.args, "load_single_floor", False) and hasattr(self, "floor_min_height"):
+            floors = [(self.floor_min_height, self.floor_max_height)] * Q
+        pos, sim, cnt = self.engine.localize_regions(q, K=K, radius=region_radius, curr=curr_grid, floor=floors)
+        out = []
+        for i in range(Q):
+            n = int(cnt[i])
+            top_pos = pos[i, :n].astype(np.int64)
+            out.append((top_pos[:1], top_pos, sim[i, :n].astype(np.float64)))
+        self._log(f"finish localizing {Q} prompts, time:{time.time() - t1}")
+        return out
+
     def weighted_cluster_centers(self, top_k_positions, top_k_similarity, eps=10, min_samples=5):
         """GESObjectNavRobot.weighted_cluster_centers (BSCAgent.py:479-497) on the GPU: DBSCAN over the top-K voxel
         positions + similarity-weighted centres -> (cluster_centers (n,3) f64, labels (K,), cluster_sizes)."""

@@ -159,6 +159,24 @@ bsc_status bsc_localize(bsc_ctx *ctx, const float *q_dev, int32_t n_queries, int
                         const int32_t *curr_host, int32_t floor_lo, int32_t floor_hi, int32_t *out_pos_host,
                         float *out_sim_host, int32_t *out_count_host);
 
+/* voxel_localized for a batch of queries that each carry their own region, as every caller in the reference's agent does
+ * (curr_grid / region_radius per call, BSCAgent.py:630,643,647; the adaptive loop :1078-1098 asks one prompt with radius 30, 40,
+ * 50): region i filters query i the way bsc_localize's scalars filter all of its queries — radius < 0 disables the sphere,
+ * otherwise a voxel passes when its integer squared distance to curr, in double, is <= radius * radius (memory_2.py:624-631);
+ * floor_lo > floor_hi disables the band, otherwise floor_lo <= h <= floor_hi (:633-640).  Scores, per-voxel max, order, outputs,
+ * limits and the resident "last localize" results (bsc_cluster_centers with NULL positions) are those of bsc_localize; a batch of
+ * equal regions is that call.  Only the rows some query can see are streamed when they are a small share of the store.
+ * BSC_E_INVALID, nothing changed: NULL regions_host, a NaN radius, reserved != 0, K / n_queries out of range. */
+typedef struct bsc_region {
+    double radius;
+    int32_t curr[3];
+    int32_t floor_lo, floor_hi;
+    int32_t reserved; /* must be 0 */
+} bsc_region;         /* 32 bytes, no implicit padding */
+bsc_status bsc_localize_regions(bsc_ctx *ctx, const float *q_dev, int32_t n_queries, int32_t K,
+                                const bsc_region *regions_host /* (Q) */, int32_t *out_pos_host, float *out_sim_host,
+                                int32_t *out_count_host);
+
 /* GESObjectNavRobot.weighted_cluster_centers (BSCAgent.py:479-497), the consumer of voxel_localized's output:
  * DBSCAN(eps, min_samples) over K top-ranked positions (scikit-learn semantics), similarity-weighted centres,
  * clusters ordered by mean similarity (stable, descending).  pos_host (K,3) / sim_host (K) NULL = cluster the first K
