@@ -62,6 +62,7 @@ SIGNATURES = {
     "bsc_localize": (_I32, [_VP, _VP, _I32, _I32, _F64, _VP, _I32, _I32, _VP, _VP, _VP]),
     "bsc_localize_regions": (_I32, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "bsc_cluster_centers": (_I32, [_VP, _I32, _I32, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
+    "bsc_cluster_centers_batch": (_I32, [_VP, _I32, _I32, _VP, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
     "bsc_frontier_mask": (_I32, [_VP, _VP, _VP]),
     "bsc_frontier_clusters": (_I32, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "bsc_import_cv_map": (_I32, [_VP, _VP]),

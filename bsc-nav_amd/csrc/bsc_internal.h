@@ -63,6 +63,7 @@ struct RadixWs {
 
 struct SurpriseWs;   // surprise.hip: scratch of bsc_flush_surprise, allocated on its first call
 struct RegionWs;     // localize.hip: scratch of bsc_localize_regions, allocated on its first call
+struct ClusterWs;    // cluster.hip: inputs, result block and pinned staging of bsc_cluster_centers(_batch), grown on demand
 
 struct bsc_ctx {
     bsc_config c;
@@ -203,6 +204,7 @@ struct bsc_ctx {
     int last_nq, last_K;            // shape of the last bsc_localize / bsc_localize_regions call (its top-K stays resident for clustering)
     RegionWs *regn;                 // bsc_localize_regions scratch (nullptr until its first call)
     int32_t last_counts[1024];
+    ClusterWs *clus;                // bsc_cluster_centers / bsc_cluster_centers_batch workspace (nullptr until the first call)
     // frontier helpers (allocated on first use, gs*gs each)
     uint8_t *fr_mask, *fr_in;
     int32_t *fr_parent, *fr_size, *fr_ord, *fr_roots, *fr_labels, *fr_first, *fr_sizes, *fr_scal;
@@ -320,6 +322,7 @@ bsc_status localize_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, 
 bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, const bsc_region *regions,
                                  int32_t *out_pos, float *out_sim, int32_t *out_count);
 void region_ws_free(bsc_ctx *x);
+void cluster_ws_free(bsc_ctx *x);    // cluster.hip
 int64_t sims_row_stride(int64_t n_rows);
 bsc_status pool_query_impl(bsc_ctx *x, const float *tokens, int32_t B, int32_t T, int32_t D, float *out);
 bsc_status read_scalars(bsc_ctx *x); // dscal -> hscal (synchronises the main stream)

@@ -64,6 +64,46 @@ def region_array(Q, radius=None, curr=None, floor=None):
     return out
 
 
+def pad_cluster_batch(pos, sim, counts=None):
+    """The (pos (Q,K,3) int32, sim (Q,K) float32, counts (Q,) int32) arrays of VoxelEngine.cluster_centers_batch from its
+    arguments (needs no context).  pos / sim are either arrays of those shapes, with counts (None: K points each, otherwise
+    0 .. K), or sequences of Q per-query arrays (n_i,3) / (n_i,) of different lengths, which are padded to the longest
+    (at least 1) with position 0 and similarity 0; counts must then be None.  Lengths that do not agree raise ValueError."""
+    ragged = not (isinstance(pos, np.ndarray) and pos.ndim == 3)
+    if ragged:
+        if counts is not None:
+            raise ValueError("counts: per-query arrays carry their own lengths")
+        pos = [np.asarray(p, np.int32).reshape(-1, 3) for p in pos]
+        sim = [np.asarray(s, np.float32).reshape(-1) for s in sim]
+        if len(pos) != len(sim):
+            raise ValueError(f"{len(pos)} position arrays for {len(sim)} similarity arrays")
+        if len(pos) == 0:
+            raise ValueError("no query")
+        for i, (p, s) in enumerate(zip(pos, sim)):
+            if len(p) != len(s):
+                raise ValueError(f"query {i}: {len(p)} positions for {len(s)} similarities")
+        cnt = np.array([len(p) for p in pos], np.int32)
+        Q, K = len(pos), max(1, int(cnt.max()))
+        P, S = np.zeros((Q, K, 3), np.int32), np.zeros((Q, K), np.float32)
+        for i in range(Q):
+            P[i, :cnt[i]] = pos[i]
+            S[i, :cnt[i]] = sim[i]
+        return P, S, cnt
+    P = np.ascontiguousarray(pos, np.int32)
+    S = np.ascontiguousarray(sim, np.float32)
+    if P.shape[2] != 3 or S.shape != P.shape[:2]:
+        raise ValueError(f"pos {P.shape} / sim {S.shape}: expected (Q,K,3) / (Q,K)")
+    Q, K = S.shape
+    if Q < 1 or K < 1:
+        raise ValueError(f"pos {P.shape}: no query or no point")
+    cnt = np.full(Q, K, np.int32) if counts is None else np.ascontiguousarray(counts, np.int32).reshape(-1)
+    if len(cnt) != Q:
+        raise ValueError(f"counts: {len(cnt)} entries for {Q} queries")
+    if np.any(cnt < 0) or np.any(cnt > K):
+        raise ValueError(f"counts outside 0..{K}")
+    return P, S, cnt
+
+
 class VoxelEngine:
     def __init__(self, height, width, grid_size, cell_size, floor_height, map_height, patch_grid, token_dim,
                  mode="exact", iter_size=50000, cache_size=10, voxel_capacity=None, token_capacity=None,
@@ -97,6 +137,7 @@ class VoxelEngine:
         _lib.check(self.lib.bsc_create(C.byref(c), device, C.c_void_p(self.stream.cuda_stream), C.byref(h)))
         self.h = h
         self.log_capacity = 0
+        self._last_localize = None      # (Q, K, counts) of the last localize call: its results stay on the GPU for clustering
         self._draw = _lib.DRAW_FN(self._draw_cb)
 
     # memory_2.py:352 — Python's global RNG, one draw per row that meets a full voxel
@@ -288,6 +329,7 @@ class VoxelEngine:
         self._enter(q)
         _lib.check(self.lib.bsc_localize(self.h, _dp(q), Q, K, -1.0 if radius is None else float(radius), _hp(curr_a),
                                          lo, hi, _hp(pos), _hp(sim), _hp(cnt)))
+        self._last_localize = (Q, K, cnt.copy())
         return pos, sim, cnt
 
     def localize_regions(self, q, K=100, radius=None, curr=None, floor=None):
@@ -301,6 +343,7 @@ class VoxelEngine:
         pos, sim, cnt = np.zeros((Q, K, 3), np.int32), np.zeros((Q, K), np.float32), np.zeros(Q, np.int32)
         self._enter(q)
         _lib.check(self.lib.bsc_localize_regions(self.h, _dp(q), Q, K, _hp(regions), _hp(pos), _hp(sim), _hp(cnt)))
+        self._last_localize = (Q, K, cnt.copy())
         return pos, sim, cnt
 
     def cluster_centers(self, pos=None, sim=None, K=None, query_index=0, eps=10.0, min_samples=5):
@@ -315,6 +358,35 @@ class VoxelEngine:
         _lib.check(self.lib.bsc_cluster_centers(self.h, query_index, K, _hp(pos), _hp(sim), float(eps), int(min_samples),
                                                 _hp(centers), _hp(labels), _hp(sizes), _hp(n)))
         return centers[:n[0]], labels.astype(np.int64), [int(v) for v in sizes[:n[0]]]
+
+    def cluster_centers_batch(self, pos=None, sim=None, counts=None, K=None, eps=10.0, min_samples=5):
+        """cluster_centers for every query of a batch in one call (bsc_cluster_centers_batch) -> one
+        (centers (n,3) f64, labels (n_i,) int64, sizes list) per query.
+        pos / sim None: the results of the last localize / localize_regions call, still on the GPU (no host copy); K
+        (default: that call's K) and counts (default: what each query found, at most K) narrow them.
+        Otherwise pos (Q,K,3) / sim (Q,K) arrays with counts (Q,) (None: K points each), or lists of per-query arrays of
+        different lengths, padded here (see pad_cluster_batch); a query without points gives no clusters."""
+        if (pos is None) != (sim is None):
+            raise ValueError("pos and sim go together (both None: the resident results of the last localize call)")
+        if pos is None:
+            if self._last_localize is None:
+                raise _lib.BscError("cluster_centers_batch: no localize call whose results could be clustered")
+            Q, last_K, last_cnt = self._last_localize
+            K = last_K if K is None else int(K)
+            cnt = np.minimum(last_cnt, K).astype(np.int32) if counts is None else np.ascontiguousarray(counts, np.int32)
+            counts_arg = None if counts is None else cnt
+        else:
+            pos, sim, cnt = pad_cluster_batch(pos, sim, counts)
+            Q, K = sim.shape
+            counts_arg = cnt
+        if len(cnt) != Q:
+            raise ValueError(f"counts: {len(cnt)} entries for {Q} queries")
+        centers, labels = np.zeros((Q, K, 3), np.float64), np.full((Q, K), -1, np.int32)
+        sizes, ncl = np.zeros((Q, K), np.int32), np.zeros(Q, np.int32)
+        _lib.check(self.lib.bsc_cluster_centers_batch(self.h, Q, K, _hp(counts_arg), _hp(pos), _hp(sim), float(eps),
+                                                      int(min_samples), _hp(centers), _hp(labels), _hp(sizes), _hp(ncl)))
+        return [(centers[i, :ncl[i]].copy(), labels[i, :cnt[i]].astype(np.int64), [int(v) for v in sizes[i, :ncl[i]]])
+                for i in range(Q)]
 
     # ---- FrontierExplorer helpers (memory_2.py:1147-1311) ----------------------------------------------
     def frontier_mask(self, navigable=None):

@@ -397,6 +397,46 @@ class VoxelTokenMemory:
         positions + similarity-weighted centres -> (cluster_centers (n,3) f64, labels (K,), cluster_sizes)."""
         return self.engine.cluster_centers(top_k_positions, top_k_similarity, eps=eps, min_samples=min_samples)
 
+    def weighted_cluster_centers_batch(self, positions, similarities, eps=10, min_samples=5):
+        """weighted_cluster_centers for several top-K lists in one call: positions / similarities are lists of per-prompt
+        arrays (n_i,3) / (n_i,) of any lengths (what voxel_localized_batch returns), or (Q,K,3) / (Q,K) arrays
+        -> list of (cluster_centers (n,3) f64, labels (n_i,), cluster_sizes).  An empty list gives no clusters."""
+        return self.engine.cluster_centers_batch(positions, similarities, eps=eps, min_samples=min_samples)
+
+    def working_memory_retrieval_batch(self, prompts, K=100, region_radius=np.inf, curr_grid=None, floors=None, eps=10,
+                                       min_samples=5, nearest_first=False):
+        """The memory side of GESObjectNavRobot.working_memory_retrival (BSCAgent.py:587-664) for several prompts / regions
+        in one go: voxel_localized_batch (same arguments, same rules) followed by weighted_cluster_centers on every
+        prompt's top-K, which never leaves the GPU in between (two synchronizes for the whole batch).
+        -> list of (cluster_centers (n,3) f64, top_k_positions (n_i,3) int64, top_k_similarity (n_i,) f64, labels (n_i,),
+        cluster_sizes), one per prompt; a prompt whose region holds no voxel gives empty arrays.
+        nearest_first  reorder each prompt's centres (and sizes) by their Euclidean distance to that prompt's curr_grid,
+                       stable, as move2textprompt_adaptive_region does (BSCAgent.py:1086-1090); needs curr_grid.
+        The adaptive-region loop (:1078-1098) is one call: prompts=[p, p, p], region_radius=(30, 40, 50), one curr_grid."""
+        t1 = time.time()
+        if nearest_first and curr_grid is None:
+            raise ValueError("nearest_first orders the centres by distance to curr_grid")
+        if isinstance(prompts, torch.Tensor) and prompts.dim() == 2:
+            q = prompts.to(self.device, torch.float32).contiguous()
+        else:
+            q = torch.cat([self._query_embedding(p) for p in prompts], 0)
+        Q = q.shape[0]
+        if floors is None and getattr(self.args, "load_single_floor", False) and hasattr(self, "floor_min_height"):
+            floors = [(self.floor_min_height, self.floor_max_height)] * Q
+        pos, sim, cnt = self.engine.localize_regions(q, K=K, radius=region_radius, curr=curr_grid, floor=floors)
+        clusters = self.engine.cluster_centers_batch(eps=eps, min_samples=min_samples)
+        curr = None if curr_grid is None else np.broadcast_to(np.asarray(curr_grid, np.float64).reshape(-1, 3), (Q, 3))
+        out = []
+        for i in range(Q):
+            n = int(cnt[i])
+            centers, labels, sizes = clusters[i]
+            if nearest_first and len(centers):
+                order = np.argsort(np.linalg.norm(centers - curr[i], axis=1), kind="stable")
+                centers, sizes = centers[order], [sizes[j] for j in order]
+            out.append((centers, pos[i, :n].astype(np.int64), sim[i, :n].astype(np.float64), labels, sizes))
+        self._log(f"finish retrieving {Q} prompts, time:{time.time() - t1}")
+        return out
+
     def long_memory_filter(self):
         """memory_2.py:693-705."""
         if getattr(self.args, "load_single_floor", False) and hasattr(self, "floor_min_height"):

@@ -186,6 +186,25 @@ bsc_status bsc_cluster_centers(bsc_ctx *ctx, int32_t query_index, int32_t K, con
                                const float *sim_host, double eps, int32_t min_samples, double *centers_host,
                                int32_t *labels_host, int32_t *sizes_host, int32_t *n_clusters_host);
 
+/* The same for every query of a batch in one call: what the agent actually asks of its memory.  working_memory_retrival
+ * (BSCAgent.py:587-664) localizes and then runs weighted_cluster_centers (:479-497, called at :649) on the top-K, and the
+ * adaptive-region loop (:1078-1098) does that chain with radius 30, 40, 50 — after bsc_localize_regions this call turns the
+ * whole batch into cluster centres with one launch (a workgroup per query), one device-to-host copy and one synchronize.
+ * Per query i the results are exactly those of bsc_cluster_centers on that query's first n_i points.
+ *   resident form  pos_host == NULL (sim_host must be NULL too): the points are the results of the last bsc_localize /
+ *                  bsc_localize_regions call, still in HBM; n_queries must equal that call's and K must be <= its K.
+ *                  n_i = min(K, results of query i), or counts_host[i] when given (0 .. that minimum).
+ *   host form      pos_host (Q,K,3) i32 and sim_host (Q,K) f32: row i holds n_i = counts_host[i] points (0 .. K; NULL: K).
+ * centers_host (Q,K,3) f64 and sizes_host (Q,K): the first n_clusters_host[i] rows of query i valid, the rest zero;
+ * labels_host (Q,K): -1 noise, and -1 from n_i on.  A query with n_i == 0 is legal: no clusters.
+ * BSC_E_INVALID, nothing written, the resident results untouched: a NULL context or output, n_queries outside 1..1024,
+ * K outside 1..1024, min_samples < 1, a NaN eps, a count out of range, exactly one of pos_host / sim_host NULL, a resident
+ * call that does not match the last localize call (or none has been made). */
+bsc_status bsc_cluster_centers_batch(bsc_ctx *ctx, int32_t n_queries, int32_t K, const int32_t *counts_host,
+                                     const int32_t *pos_host, const float *sim_host, double eps, int32_t min_samples,
+                                     double *centers_host, int32_t *labels_host, int32_t *sizes_host,
+                                     int32_t *n_clusters_host);
+
 /* FrontierExplorer helpers (memory_2.py:1147-1311) on the resident top-down colour map (cv_map, kept by bsc_ingest).
  *   bsc_frontier_mask     is_unknown / is_known / build_navigable_mask / find_frontiers (:1165-1207):
  *                         mask_host[x*gs+y] bit0 = known (cv_map[x,y].sum() != 0), bit1 = frontier cell (known, navigable,
