@@ -359,7 +359,8 @@ __global__ __launch_bounds__(TPB) void k_surp_task(SurpArgs a)
         __syncthreads();
         if (rr < r1) {
             const float xi = a.inv[rr];
-            if (xi != xi || N == 0) a.acc[rr] = (N == 0);     // zero token: NaN with neighbours, +inf without (:375-376)
+            // zero token: NaN with neighbours; no neighbour token: +inf (:375-377), compared like any other value (:500)
+            if (xi != xi || N == 0) a.acc[rr] = (N == 0) && (double)INFINITY > a.sthr;
             else s_dotrows[atomicAdd(&s_ndot, 1)] = rr;
         }
         __syncthreads();

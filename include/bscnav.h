@@ -106,7 +106,9 @@ bsc_status bsc_flush(bsc_ctx *ctx, bsc_draw_fn draw, void *user);
  * overwrites the slot of the smallest 1 - cos (:448-468), then the group is merged by the components of
  * sim > boring_threshold (:386-446).  The cache is cleared as by bsc_flush; no draws.  Exact mode only (BSC_E_STATE);
  * BSC_E_INVALID for neighbor_radius outside [0, 3], a NaN threshold, cache_size > 64, or a radius whose
- * ((2r+1)^3 - 1) x cache_size neighbour tokens (8 bytes each) plus one token exceed 48 KiB of LDS. */
+ * ((2r+1)^3 - 1) x cache_size neighbour tokens (8 bytes each) plus one token exceed 48 KiB of LDS.  Infinite thresholds
+ * are legal and compare as in Python: surprise_threshold = +inf only creates groups (+inf > +inf is false, also for a row
+ * without neighbour tokens), -inf accepts every row whose surprise is not NaN; boring_threshold = +inf never merges. */
 bsc_status bsc_flush_surprise(bsc_ctx *ctx, int32_t neighbor_radius, double surprise_threshold, double boring_threshold);
 
 /* counters (host sync): out[0]=max_id out[1]=iter_id out[2]=store voxels out[3]=store tokens

@@ -90,8 +90,9 @@ def replay(st, cache_pos, cache_feat, cache_dis, radius=1, surprise_threshold=0.
                 counts["replace_nan"] += 1
             else:
                 k = int(np.argmin(cd))
-                srt = np.sort(cd)
-                margins["argmin"] = min(margins["argmin"], float(srt[1] - srt[0]))
+                if len(cd) > 1:      # cache_size 1: nothing to choose between
+                    srt = np.sort(cd)
+                    margins["argmin"] = min(margins["argmin"], float(srt[1] - srt[0]))
             counts["replace"] += 1
             feats[k], dists[k], merged[k] = x.copy(), d, False
         n = len(feats)

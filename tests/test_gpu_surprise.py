@@ -29,7 +29,8 @@ def assert_store_matches(got, pos, cnt, feat, dis, merged, tag=""):
 def _direct_engine(z):
     import bsc_nav_amd as B
     eng = B.VoxelEngine(48, 64, int(z["gs"]), float(z["cell"]), float(z["floor_height"]), float(z["map_height"]), 16,
-                        int(z["D"]), mode="exact", iter_size=int(z["iter_size"]), cache_size=int(z["cache_size"]))
+                        int(z["D"]), mode="exact", iter_size=int(z["iter_size"]), cache_size=int(z["cache_size"]),
+                        voxel_capacity=int(z["voxel_capacity"]) if "voxel_capacity" in z else None)
     vp = z["vox_pos"]
     eng.import_rgb(vp, np.zeros((len(vp), 3), np.uint8), np.zeros(len(vp), np.float32))
     eng.import_store(z["prior_pos"], z["prior_cnt"], z["prior_feat"], z["prior_dis"])
