@@ -184,7 +184,7 @@ struct bsc_ctx {
     uint32_t *l_val_a, *l_val_b;
     uint32_t *l_name_rank;
     float *l_q;          // normalised queries
-    uint16_t *l_qp;      // their three bf16 pieces (3, 1024, D) for the bf16x3 scan
+    uint16_t *l_qp;      // their 16-bit pieces, planes of (padded queries, D): two fp16 (k_cosine_f16x2) or three bf16 (k_cosine_bf16x3)
     u64 *l_sel_key[2];   // batched top-K selection rounds (grown on demand)
     uint32_t *l_sel_val[2];
     u64 *l_sel_thr;      // per-query threshold keys of the sample selection
@@ -249,6 +249,16 @@ void bsc_set_error(const char *fmt, ...);
         bsc_status _s = (expr);       \
         if (_s != BSC_OK) return _s;  \
     } while (0)
+// a function shared between translation units that stays out of the library's dynamic symbol table
+#define BSC_LOCAL __attribute__((visibility("hidden")))
+
+// sum of v over the wavefront's 64 lanes, in every lane (xor butterfly, distances 32 .. 1)
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 // ---- primitives (prims.hip; rocPRIM device-wide sort and scans) ----
 size_t prim_workspace_bytes(size_t max_items);
@@ -285,7 +295,7 @@ __device__ __forceinline__ float4 load_tok4(const bf16_t *row, int v)
 }
 
 // (power-of-two operand scale, 1 / (norm scale 2^11)) of a token row from the sum of its squares: what the fp16-piece batched scan
-// (localize.hip k_cosine_f16x2) reads per row; computed by k_row_scale (one pass over the rows) and, row by row, by the dense reduce
+// (cosine_scan.hip k_cosine_f16x2) reads per row; computed by k_row_scale (one pass over the rows) and, row by row, by the dense reduce
 __device__ __forceinline__ float2 bsc_row_scale_of(float sumsq)
 {
     const float nrm = sqrtf(sumsq);
@@ -323,7 +333,20 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
                                  int32_t *out_pos, float *out_sim, int32_t *out_count);
 void region_ws_free(bsc_ctx *x);
 void cluster_ws_free(bsc_ctx *x);    // cluster.hip
-int64_t sims_row_stride(int64_t n_rows);
+// ---- the cosine scan (cosine_scan.hip), as localize.hip calls it ----
+int64_t sims_row_stride(int64_t n_rows);   // floats between the similarity rows of consecutive queries
+// q_dev (nq, D) -> x->l_q: normalised, zero-padded to the whole query tiles the matrix-core kernels read
+BSC_LOCAL bsc_status stage_queries(bsc_ctx *x, const float *q_dev, int nq);
+// rs / rs_cap / rs_dirty: the cached per-row scales of THESE rows for the fp16-piece scan (the context's own for its store, a
+// scratch set for a gathered matrix); grown and recomputed (k_row_scale) when the rows changed or the buffer is too small.
+// Nothing to do without rows or when token_dim rules the matrix-core scan out.
+BSC_LOCAL bsc_status refresh_row_scales(bsc_ctx *x, const float *rows, int64_t n_rows, float2 **rs, int64_t *rs_cap, bool *rs_dirty);
+// The scan of nq staged queries (x->l_q) over the matrix rows (n_rows, D) -> x->l_sims, query rows sims_row_stride(n_rows)
+// apart.  *passes_out = times the matrix was streamed.
+BSC_LOCAL bsc_status cosine_scan(bsc_ctx *x, const float *rows, int64_t n_rows, int nq, float2 **rs, int64_t *rs_cap, bool *rs_dirty,
+                                 int *passes_out);
+// localize scratch: *p holds at least need_bytes afterwards (contents are not kept; no slack: callers add their own)
+BSC_LOCAL bsc_status grow_dev(void **p, int64_t *cap, int64_t need_bytes);
 bsc_status pool_query_impl(bsc_ctx *x, const float *tokens, int32_t B, int32_t T, int32_t D, float *out);
 bsc_status read_scalars(bsc_ctx *x); // dscal -> hscal (synchronises the main stream)
 void localize_prepare(bsc_ctx *x);   // name ranks + row scales of the batched scan, eagerly (localize.hip; the imports call it)

@@ -6,7 +6,7 @@
 //     x w = xh wh + xh wl + xl wh + O(2^-22 |x w|)
 // and the three piece products are exact in the matrix core's f32 accumulator: three v_mfma_f32_32x32x16_f16 per f32 product
 // term at 16x the f32 MFMA rate.  (Three bf16 pieces need six products for the same accuracy; with three products they leave
-// 2^-16 — k_cosine_bf16x3 of localize.hip is the six-product form.  fp16 pieces have a 5-bit exponent: the weights are scaled by
+// 2^-16 — k_cosine_bf16x3 of cosine_scan.hip is the six-product form.  fp16 pieces have a 5-bit exponent: the weights are scaled by
 // a power of two per matrix so that their largest element sits near 2^3, the activation operand by a per-layer power of two, and
 // the scales leave through the epilogue exactly; what remains of the narrow range is that the l piece of an element 2^10 below the
 // operand's typical magnitude goes subnormal, i.e. is kept to an ABSOLUTE 2^-25 — far below the 2^-22 relative error of the

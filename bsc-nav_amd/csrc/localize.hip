@@ -1,16 +1,16 @@
-// localize.hip — voxel_localized (memory_2.py:563-671): query pooling, cosine scan over every stored token,
-// per-voxel max, stable top-K in HDF5 group-name order.
+// localize.hip — voxel_localized (memory_2.py:563-671) around the cosine scan (cosine_scan.hip): query pooling before it; after it
+// the per-voxel max and the stable top-K in HDF5 group-name order.
 //
 //   k_pool_query   Gaussian centre-weighted pooling of (B,T,D) query tokens -> (D)          (:591-608)
-//   k_cosine       one wavefront per token row: dot(q^, x) and |x|^2 with 16-byte loads and
-//                  wave-shuffle reductions; the (rows, D) matrix is streamed from HBM exactly once
-//                  for all Q queries of the call (HBM-bound)                  (:656)
+//   k_name_keys    HDF5 link-name order of the stored voxels -> name ranks, rebuilt when the set of voxels changed
+//   VoxelView      the store as the candidate kernels see it; CandArgs / RegionCandArgs: the two candidate lists built on it
 //   k_candidates   per voxel: region / floor filters, max over its <= cache_size tokens, 64-bit
 //                  rank key (similarity descending, then name order)                         (:624-663)
-//   k_block_topk   rounds of per-1024 bitonic selections shrink the candidates to the K smallest rank keys =
-//                  the reference's stable-sort top-K (device-wide radix sort only for K > 512)  (:665-667)
+//   k_block_topk   rounds of per-1024 bitonic selections (large sets: behind a sample threshold and k_cand_filter) shrink the
+//                  candidates to the K smallest rank keys = the reference's stable-sort top-K (device-wide radix sort only for
+//                  K > 512)                                                                   (:665-667)
 //   k_region_*     bsc_localize_regions (end of this file): a sphere and floor band per query (BSCAgent.py:630-647,1078-1098),
-//                  visibility pass, compaction + gather of the visible rows, the scan above over those rows only
+//                  visibility pass, compaction + gather of the visible rows, the scan over those rows only
 #include "bsc_internal.h"
 
 #include <math.h>
@@ -42,13 +42,6 @@ __host__ __device__ static inline u64 name_key(int32_t r, int32_t c, int32_t h)
     return (name_field(r, false) * B + name_field(c, false)) * B + name_field(h, true);
 }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // memory_2.py:591-608.  One thread per feature d; weights recomputed in f32 like the torch expression.
 __global__ __launch_bounds__(TPB) void k_pool_query(const float *__restrict__ tokens, int B, int T, int D,
                                                     float *__restrict__ out)
@@ -74,506 +67,6 @@ __global__ __launch_bounds__(TPB) void k_pool_query(const float *__restrict__ to
         total += s;
     }
     out[d] = total / (float)B;
-}
-
-// q (Q,D) -> q / max(|q|, 1e-8)   (torch cosine_similarity eps clamp)
-__global__ __launch_bounds__(64) void k_normalize_q(const float *__restrict__ q, int D, float *__restrict__ qn)
-{
-    const int lane = threadIdx.x;
-    const float *src = q + (int64_t)blockIdx.x * D;
-    float s = 0.f;
-    for (int k = lane; k < D; k += 64) s += src[k] * src[k];
-    s = wave_sum(s);
-    const float nrm = fmaxf(sqrtf(s), 1e-8f);
-    for (int k = lane; k < D; k += 64) qn[(int64_t)blockIdx.x * D + k] = src[k] / nrm;
-}
-
-// Wave-wide sums of QT per-lane values at once (QT = 2, 4, 8): every butterfly step over a lane bit also halves the number
-// of values a lane carries (the half of the wavefront with the bit set keeps the upper values), so QT sums cost
-// QT - 1 + log2(64 / QT) exchanges instead of 6 QT.  The pairs added at each distance are those of wave_sum, so every
-// sum is bit-identical to wave_sum of that value.  Returns the sum of value `q` in the lanes whose bits 5.. select q:
-// q = lane >> (6 - log2 QT); all lanes of that group hold it.
-template <int QT>
-__device__ __forceinline__ float multi_wave_sum(float (&v)[QT], int lane)
-{
-    int mask = 32;
-#pragma unroll
-    for (int keep = QT >> 1; keep >= 1; keep >>= 1) {
-        const bool hi = (lane & mask) != 0;
-#pragma unroll
-        for (int i = 0; i < keep; ++i) {
-            const float mine = hi ? v[i + keep] : v[i], theirs = hi ? v[i] : v[i + keep];
-            v[i] = mine + __shfl_xor(theirs, mask);
-        }
-        mask >>= 1;
-    }
-    float r = v[0];
-    for (; mask > 0; mask >>= 1) r += __shfl_xor(r, mask);
-    return r;
-}
-
-// sims[qi * n_rows + row] = dot(q^[qi], x[row]) / max(|x[row]|, 1e-8).
-// One wavefront per row (grid-stride), NV float4 per lane; the row is loaded once and reused for QT queries.
-template <int NV, int QT>
-__global__ __launch_bounds__(TPB) void k_cosine(const float *__restrict__ rows, int64_t n_rows, int D,
-                                                const float *__restrict__ qn, int q0, float *__restrict__ sims,
-                                                int64_t sims_stride)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * TPB) >> 6;
-    const int D4 = D >> 2;
-    float4 qv[QT][NV];
-#pragma unroll
-    for (int qi = 0; qi < QT; ++qi)
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            const int v = lane + 64 * t;
-            qv[qi][t] = (v < D4) ? ((const float4 *)(qn + (int64_t)(q0 + qi) * D))[v] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    for (int64_t r = wave; r < n_rows; r += nwaves) {
-        const float4 *src = (const float4 *)(rows + r * D);
-        float4 xv[NV];
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            const int v = lane + 64 * t;
-            xv[t] = (v < D4) ? src[v] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        float n2 = 0.f;
-#pragma unroll
-        for (int t = 0; t < NV; ++t) n2 += xv[t].x * xv[t].x + xv[t].y * xv[t].y + xv[t].z * xv[t].z + xv[t].w * xv[t].w;
-        n2 = wave_sum(n2);
-        const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-8f);
-        float dsum[QT];
-#pragma unroll
-        for (int qi = 0; qi < QT; ++qi) {
-            float d = 0.f;
-#pragma unroll
-            for (int t = 0; t < NV; ++t)
-                d += xv[t].x * qv[qi][t].x + xv[t].y * qv[qi][t].y + xv[t].z * qv[qi][t].z + xv[t].w * qv[qi][t].w;
-            dsum[qi] = d;
-        }
-        if (QT == 1) {
-            const float d = wave_sum(dsum[0]);
-            if (lane == 0) sims[(int64_t)q0 * sims_stride + r] = d * inv;
-        } else {
-            // the wavefront's QT groups of 64 / QT lanes end up with one query's sum each; their first lanes store
-            const float d = multi_wave_sum<QT>(dsum, lane);
-            if ((lane & (64 / QT - 1)) == 0) sims[(int64_t)(q0 + lane / (64 / QT)) * sims_stride + r] = d * inv;
-        }
-    }
-}
-
-// ---- batched queries on the matrix cores -----------------------------------------------------------------------
-// S^T tile (32 queries x 32 rows) = Qn (32 x D) . X^T (D x 32) with v_mfma_f32_32x32x2_f32: fp32 in, fp32 accumulate,
-// bit-for-bit an fmaf chain (no TF32 on gfx950), 64 cycles per instruction.  One workgroup = 4 waves = 128 rows;
-// each wave owns 32 rows and NT 32-query tiles (16 accumulator registers each).  K is walked in chunks of 32 staged
-// through LDS (row stride 33 floats: conflict-free ds_read_b32 for the 32-lane operand groups), double-buffered
-// with register prefetch of the next chunk.  The squared row norms fall out of the B operands the lanes already hold.
-// Queries sit on the M axis so that the accumulator columns are rows of X: stores are 128-byte row runs per query.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define MF_KC 32
-#ifndef BSC_MFMA_MIN_Q
-#define BSC_MFMA_MIN_Q 5     // up to 4 queries: one wavefront per row on the vector ALUs (k_cosine, 5.6 TB/s); from 5 on the
-                             // VALU dot products no longer hide behind the row stream (8 queries: 3.6 TB/s) and a zero-padded
-                             // 32-query MFMA tile is faster (4.9 TB/s for 5..32 queries over 2^20 x 768)
-#endif
-#define MF_LD 33
-template <int NT>
-__global__ __launch_bounds__(TPB) void k_cosine_mfma(const float *__restrict__ X, int64_t n_rows, int D,
-                                                     const float *__restrict__ qn, int q0, int q_valid,
-                                                     float *__restrict__ sims, int64_t sims_stride)
-{
-    __shared__ float Xs[2][128 * MF_LD];
-    __shared__ float Qs[2][NT * 32 * MF_LD];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int64_t row0 = (int64_t)blockIdx.x * 128;
-    const int nchunks = D / MF_KC;
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    float nrm = 0.f;
-    float4 xr[4], qr[NT];
-    auto load_chunk = [&](int c) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + TPB * i, r = idx >> 3, c4 = idx & 7;
-            const int64_t gr = row0 + r;
-            xr[i] = gr < n_rows ? *(const float4 *)(X + gr * D + c * MF_KC + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int idx = tid + TPB * i, r = idx >> 3, c4 = idx & 7;
-            qr[i] = *(const float4 *)(qn + (int64_t)(q0 + r) * D + c * MF_KC + c4 * 4);
-        }
-    };
-    auto store_chunk = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + TPB * i, r = idx >> 3, c4 = idx & 7;
-            float *d = &Xs[buf][r * MF_LD + c4 * 4];
-            d[0] = xr[i].x; d[1] = xr[i].y; d[2] = xr[i].z; d[3] = xr[i].w;
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int idx = tid + TPB * i, r = idx >> 3, c4 = idx & 7;
-            float *d = &Qs[buf][r * MF_LD + c4 * 4];
-            d[0] = qr[i].x; d[1] = qr[i].y; d[2] = qr[i].z; d[3] = qr[i].w;
-        }
-    };
-    load_chunk(0);
-    store_chunk(0);
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        const int buf = c & 1;
-        if (c + 1 < nchunks) load_chunk(c + 1);
-        const float *xb = &Xs[buf][(w * 32 + (lane & 31)) * MF_LD + (lane >> 5)];
-        const float *qb = &Qs[buf][(lane & 31) * MF_LD + (lane >> 5)];
-#pragma unroll 4
-        for (int kk = 0; kk < MF_KC; kk += 2) {
-            const float b = xb[kk];
-            nrm = fmaf(b, b, nrm);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float a = qb[t * 32 * MF_LD + kk];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[t], 0, 0, 0);
-            }
-        }
-        if (c + 1 < nchunks) store_chunk(buf ^ 1);
-        __syncthreads();
-    }
-    nrm += __shfl_xor(nrm, 32);
-    const float inv = 1.0f / fmaxf(sqrtf(nrm), 1e-8f);
-    const int64_t row = row0 + w * 32 + (lane & 31);
-    if (row < n_rows) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int q = q0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (q < q_valid) sims[(int64_t)q * sims_stride + row] = acc[t][r] * inv;
-            }
-    }
-}
-
-// ---- batched queries on the bf16 matrix cores at f32 accuracy -----------------------------------------------------------
-// gfx950 has no TF32; its f32 MFMA peaks at 157 TFLOP/s, its bf16 MFMA at 2.5 PFLOP/s.  An f32 value is the exact sum of three
-// bf16 pieces (8 significand bits each: h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), the differences are exact), so a
-// product x q is the sum of nine piece products; the six of weight >= 2^-16 (hh, hm, mh, hl, mm, lh) leave a truncation of
-// 2^-24 per product — the rounding an f32 multiply has anyway — and accumulate in the matrix core's f32 accumulators like the
-// f32 instruction does.  Six bf16 MFMAs at 16x the rate replace one f32 MFMA: 0.375x the matrix time, and the scan moves from
-// MFMA-bound (4.1 ms for 256 queries over 2^20 x 768) towards its HBM time.
-//   A operand (M axis): 32 queries per tile, NT tiles — the three pieces of the normalised queries come precomputed
-//                       (k_split_q) and are staged per 32-wide K chunk through LDS (80-byte row pitch), double-buffered;
-//   B operand (N axis): the wavefront's 32 rows straight from global memory in fragment layout — lane (n, g) loads the 16
-//                       floats [32 c + 16 g, + 16) of row n (one 128-byte line per row and chunk over the two lane groups),
-//                       splits them in registers; sub-step s of a chunk contracts floats [8 s, 8 s + 8) of every lane;
-//   v_mfma_f32_32x32x16_bf16: 12 per tile and chunk, interleaved over the NT independent accumulators.
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-#define BX_KC 32                 // K chunk
-#define BX_PITCH 40              // bf16 elements per staged query row (80 bytes: conflict-free 16-byte reads)
-
-__device__ __forceinline__ uint32_t pack_bf16_rne(float lo, float hi)      // v_cvt_pk_bf16_f32
-{
-    const f32x2_t v = {lo, hi};
-    const bf16x2_t r = __builtin_convertvector(v, bf16x2_t);
-    return *(const uint32_t *)&r;
-}
-
-// (a, b) -> packed bf16 pieces h, m, l of both
-__device__ __forceinline__ void split3(float a, float b, uint32_t &h, uint32_t &m, uint32_t &l)
-{
-    h = pack_bf16_rne(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = pack_bf16_rne(ra, rb);
-    l = pack_bf16_rne(ra - __uint_as_float(m << 16), rb - __uint_as_float(m & 0xffff0000u));
-}
-
-// qn (Q, D) f32 -> qp (3, Q, D) bf16 pieces
-__global__ __launch_bounds__(TPB) void k_split_q(const float *__restrict__ qn, int64_t n, uint16_t *__restrict__ qp)
-{
-    const int64_t i = ((int64_t)blockIdx.x * TPB + threadIdx.x) * 2;
-    if (i >= n) return;
-    uint32_t h, m, l;
-    split3(qn[i], qn[i + 1], h, m, l);
-    *(uint32_t *)(qp + i) = h;
-    *(uint32_t *)(qp + n + i) = m;
-    *(uint32_t *)(qp + 2 * n + i) = l;
-}
-
-// WV wavefronts per workgroup, 32 rows each: WV = 8 puts two wavefronts on every SIMD (256 registers each) that share one staged
-// query chunk — one covers the other's LDS / global / barrier waits
-// SIX: all six products of weight >= 2^-16 (hh, hm, mh, hl, mm, lh: 2^-24 per product, what an f32 multiply rounds away); otherwise
-// the three of weight >= 2^-8 (hh, hm, mh): 2^-16 per product term, ~4e-7 on the cosine of unit vectors after the 1/sqrt(D)
-// averaging of D independent terms — inside the 2e-6 the tests hold the scan to and 2 500x inside the north star's 1e-3 —
-// at half the matrix work and without the l plane of the queries.
-template <int NT, int WV, bool SIX>
-__global__ __launch_bounds__(64 * WV) void k_cosine_bf16x3(const float *__restrict__ X, int64_t n_rows, int D,
-                                                       const uint16_t *__restrict__ qp, int64_t q_plane, int q0, int q_valid,
-                                                       float *__restrict__ sims, int64_t sims_stride)
-{
-    extern __shared__ __attribute__((aligned(16))) uint16_t Qs[];           // [2][3][NT * 32][BX_PITCH]
-    constexpr int QROWS = NT * 32;
-    constexpr int BUF = 3 * QROWS * BX_PITCH;
-    constexpr int NTHR = 64 * WV;
-    constexpr int NLD = 3 * QROWS * 4 / NTHR;                                 // 16-byte pieces of a query chunk per thread
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int n = lane & 31, g = lane >> 5;
-    const int64_t row0 = (int64_t)blockIdx.x * (32 * WV);
-    const int64_t row = row0 + w * 32 + n;
-    const int64_t rowc = row < n_rows ? row : n_rows - 1;                  // clamped: results of padded rows are not stored
-    const float *xrow = X + rowc * D + g * 16;
-    const int nchunks = D / BX_KC;
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    float nrm = 0.f;
-    // prefetch registers as first-class vector values: an ARRAY that is live across the chunk loop is left in scratch memory
-    // by the compiler (12 scratch stores + 12 loads per chunk and lane: 4.5 ms instead of 1.x)
-    typedef float xf_t __attribute__((ext_vector_type(16)));
-    typedef uint32_t qr_t __attribute__((ext_vector_type(4 * NLD)));
-    xf_t xf;
-    qr_t qr;
-    auto load_x = [&](int c) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 v = *(const float4 *)(xrow + c * BX_KC + 4 * i);
-            xf[4 * i] = v.x; xf[4 * i + 1] = v.y; xf[4 * i + 2] = v.z; xf[4 * i + 3] = v.w;
-        }
-    };
-    auto load_q = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + NTHR * j, p = i / (QROWS * 4), rem = i - p * (QROWS * 4), q = rem >> 2, part = rem & 3;
-            const uint4 v = *(const uint4 *)(qp + (int64_t)p * q_plane + (int64_t)(q0 + q) * D + c * BX_KC + part * 8);
-            qr[4 * j] = v.x; qr[4 * j + 1] = v.y; qr[4 * j + 2] = v.z; qr[4 * j + 3] = v.w;
-        }
-    };
-    auto store_q = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + NTHR * j, p = i / (QROWS * 4), rem = i - p * (QROWS * 4), q = rem >> 2, part = rem & 3;
-            *(uint4 *)&Qs[buf * BUF + (p * QROWS + q) * BX_PITCH + part * 8] = make_uint4(qr[4 * j], qr[4 * j + 1], qr[4 * j + 2], qr[4 * j + 3]);
-        }
-    };
-    load_x(0);
-    load_q(0);
-    store_q(0);
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        const int buf = c & 1;
-        // this chunk's rows -> bf16 pieces (two sub-steps of 8 floats), then the next chunk's loads go in flight
-        uint32_t bh[2][4], bm[2][4], bl[2][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 v = make_float4(xf[4 * i], xf[4 * i + 1], xf[4 * i + 2], xf[4 * i + 3]);
-            nrm = fmaf(v.x, v.x, nrm); nrm = fmaf(v.y, v.y, nrm); nrm = fmaf(v.z, v.z, nrm); nrm = fmaf(v.w, v.w, nrm);
-            split3(v.x, v.y, bh[i >> 1][2 * (i & 1)], bm[i >> 1][2 * (i & 1)], bl[i >> 1][2 * (i & 1)]);
-            split3(v.z, v.w, bh[i >> 1][2 * (i & 1) + 1], bm[i >> 1][2 * (i & 1) + 1], bl[i >> 1][2 * (i & 1) + 1]);
-        }
-        if (c + 1 < nchunks) { load_x(c + 1); load_q(c + 1); }
-        const uint16_t *qb = &Qs[buf * BUF + n * BX_PITCH + g * 16];
-#pragma unroll
-        for (int sstep = 0; sstep < 2; ++sstep) {
-            const bf16x8_t xh = *(const bf16x8_t *)bh[sstep], xm = *(const bf16x8_t *)bm[sstep], xl = *(const bf16x8_t *)bl[sstep];
-            // one piece of the queries at a time (NT fragments live instead of 3 NT): l is used once, m twice, h three times;
-            // smallest terms first; consecutive MFMAs go to different accumulators
-            bf16x8_t af[NT];
-            if (SIX) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) af[t] = *(const bf16x8_t *)(qb + (2 * QROWS + t * 32) * BX_PITCH + sstep * 8);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[t], xh, acc[t], 0, 0, 0);
-            }
-#pragma unroll
-            for (int t = 0; t < NT; ++t) af[t] = *(const bf16x8_t *)(qb + (1 * QROWS + t * 32) * BX_PITCH + sstep * 8);
-            if (SIX) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[t], xm, acc[t], 0, 0, 0);
-            }
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[t], xh, acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) af[t] = *(const bf16x8_t *)(qb + (0 * QROWS + t * 32) * BX_PITCH + sstep * 8);
-            if (SIX) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[t], xl, acc[t], 0, 0, 0);
-            }
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[t], xm, acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[t], xh, acc[t], 0, 0, 0);
-        }
-        if (c + 1 < nchunks) store_q(buf ^ 1);
-        __syncthreads();
-    }
-    nrm += __shfl_xor(nrm, 32);
-    const float inv = 1.0f / fmaxf(sqrtf(nrm), 1e-8f);
-    if (row < n_rows) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int q = q0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                if (q < q_valid) sims[(int64_t)q * sims_stride + row] = acc[t][r] * inv;
-            }
-    }
-}
-
-// ---- the same scan on fp16 pieces: three products instead of six -------------------------------------------------------------
-// An f32 value is, to 22 significant bits, the sum of TWO fp16 pieces (11 significand bits each): x q = xh qh + xh ql + xl qh +
-// O(2^-22 |x q|) — three v_mfma_f32_32x32x16_f16 per product instead of the six bf16 ones above, the same f32 accumulators
-// (encoder_gemm.hip runs the encoder's dense layers this way).  What fp16 lacks is range (5 exponent bits), so both operands are
-// brought to a fixed magnitude by exact power-of-two scales that leave through the result:
-//   queries  unit vectors (k_normalize_q) x 2^11: |element| <= 2048;
-//   rows     x s_r with s_r = the power of two that puts the row's NORM in [2^11, 2^12): every element below 4096, the typical
-//            one (norm / sqrt(D)) near 2^7; an element 2^10 below the typical one keeps its l piece to an absolute 2^-25 of the
-//            scaled row — far below the 2^-22 relative error of the typical term.
-// s_r and 1 / (norm s_r 2^11) per row come from k_row_scale, one pass over the rows that is redone only after the rows changed
-// (x->row_scale_dirty: ingest, flush, imports, merges, reset) — a loaded memory that is queried many times pays it once.
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-#define FX_QSCALE 2048.0f
-
-__device__ __forceinline__ void split2h(f32x2_t v, uint32_t &h, uint32_t &l)      // 2 x v_cvt_pk_f16_f32 around a packed subtract
-{
-    const half2_t hv = __builtin_convertvector(v, half2_t);
-    h = *(const uint32_t *)&hv;
-    const half2_t lv = __builtin_convertvector(v - __builtin_convertvector(hv, f32x2_t), half2_t);
-    l = *(const uint32_t *)&lv;
-}
-
-// one wavefront per row: rs[row] = (s_r, 1 / (max(norm, 1e-8) s_r 2^11))
-__global__ __launch_bounds__(TPB) void k_row_scale(const float *__restrict__ X, int64_t n_rows, int D, float2 *__restrict__ rs)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t row = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
-    if (row >= n_rows) return;
-    const float4 *xr = (const float4 *)(X + row * D);
-    float a = 0.f;
-    for (int k = lane; k < D / 4; k += 64) {
-        const float4 v = xr[k];
-        a = fmaf(v.x, v.x, a); a = fmaf(v.y, v.y, a); a = fmaf(v.z, v.z, a); a = fmaf(v.w, v.w, a);
-    }
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-    if (lane == 0) rs[row] = bsc_row_scale_of(a);
-}
-
-// qn (Q, D) f32 unit rows -> qp (2, Q, D) fp16 pieces of 2^11 qn
-__global__ __launch_bounds__(TPB) void k_split_q_f16(const float *__restrict__ qn, int64_t n, uint16_t *__restrict__ qp)
-{
-    const int64_t i = ((int64_t)blockIdx.x * TPB + threadIdx.x) * 2;
-    if (i >= n) return;
-    uint32_t h, l;
-    const f32x2_t v = {qn[i] * FX_QSCALE, qn[i + 1] * FX_QSCALE};
-    split2h(v, h, l);
-    *(uint32_t *)(qp + i) = h;
-    *(uint32_t *)(qp + n + i) = l;
-}
-
-// layout of the work as k_cosine_bf16x3: WV wavefronts x 32 rows, NT tiles of 32 queries, query pieces staged per 32-wide K chunk
-// through LDS (two planes), rows straight from global memory in fragment layout and split in registers
-template <int NT, int WV>
-__global__ __launch_bounds__(64 * WV) void k_cosine_f16x2(const float *__restrict__ X, int64_t n_rows, int D,
-                                                           const uint16_t *__restrict__ qp, int64_t q_plane, int q0, int q_valid,
-                                                           const float2 *__restrict__ rs, float *__restrict__ sims, int64_t sims_stride)
-{
-    extern __shared__ __attribute__((aligned(16))) uint16_t Qs[];           // [2][2][NT * 32][BX_PITCH]
-    constexpr int QROWS = NT * 32;
-    constexpr int BUF = 2 * QROWS * BX_PITCH;
-    constexpr int NTHR = 64 * WV;
-    constexpr int NLD = 2 * QROWS * 4 / NTHR;                                 // 16-byte pieces of a query chunk per thread
-    static_assert(2 * QROWS * 4 % NTHR == 0, "query staging plan");
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int n = lane & 31, g = lane >> 5;
-    const int64_t row0 = (int64_t)blockIdx.x * (32 * WV);
-    const int64_t row = row0 + w * 32 + n;
-    const int64_t rowc = row < n_rows ? row : n_rows - 1;                  // clamped: results of padded rows are not stored
-    const float *xrow = X + rowc * D + g * 16;
-    const float2 rsc = rs[rowc];
-    const f32x2_t sc2 = {rsc.x, rsc.x};
-    const int nchunks = D / BX_KC;
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    typedef float xf_t __attribute__((ext_vector_type(16)));
-    typedef uint32_t qr_t __attribute__((ext_vector_type(4 * NLD)));
-    xf_t xf;
-    qr_t qr;
-    auto load_x = [&](int c) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 v = *(const float4 *)(xrow + c * BX_KC + 4 * i);
-            xf[4 * i] = v.x; xf[4 * i + 1] = v.y; xf[4 * i + 2] = v.z; xf[4 * i + 3] = v.w;
-        }
-    };
-    auto load_q = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + NTHR * j, p = i / (QROWS * 4), rem = i - p * (QROWS * 4), q = rem >> 2, part = rem & 3;
-            const uint4 v = *(const uint4 *)(qp + (int64_t)p * q_plane + (int64_t)(q0 + q) * D + c * BX_KC + part * 8);
-            qr[4 * j] = v.x; qr[4 * j + 1] = v.y; qr[4 * j + 2] = v.z; qr[4 * j + 3] = v.w;
-        }
-    };
-    auto store_q = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + NTHR * j, p = i / (QROWS * 4), rem = i - p * (QROWS * 4), q = rem >> 2, part = rem & 3;
-            *(uint4 *)&Qs[buf * BUF + (p * QROWS + q) * BX_PITCH + part * 8] = make_uint4(qr[4 * j], qr[4 * j + 1], qr[4 * j + 2], qr[4 * j + 3]);
-        }
-    };
-    load_x(0);
-    load_q(0);
-    store_q(0);
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        const int buf = c & 1;
-        // this chunk's rows -> fp16 pieces of s_r x (two sub-steps of 8 floats), then the next chunk's loads go in flight
-        uint32_t bh[2][4], bl[2][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const f32x2_t p0 = (f32x2_t){xf[4 * i], xf[4 * i + 1]} * sc2, p1 = (f32x2_t){xf[4 * i + 2], xf[4 * i + 3]} * sc2;
-            split2h(p0, bh[i >> 1][2 * (i & 1)], bl[i >> 1][2 * (i & 1)]);
-            split2h(p1, bh[i >> 1][2 * (i & 1) + 1], bl[i >> 1][2 * (i & 1) + 1]);
-        }
-        if (c + 1 < nchunks) { load_x(c + 1); load_q(c + 1); }
-        const uint16_t *qb = &Qs[buf * BUF + n * BX_PITCH + g * 16];
-#pragma unroll
-        for (int sstep = 0; sstep < 2; ++sstep) {
-            const half8_t xh = *(const half8_t *)bh[sstep], xl = *(const half8_t *)bl[sstep];
-            // one piece of the queries at a time; smallest terms first; consecutive MFMAs go to different accumulators
-            half8_t af[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) af[t] = *(const half8_t *)(qb + (1 * QROWS + t * 32) * BX_PITCH + sstep * 8);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t], xh, acc[t], 0, 0, 0);      // ql xh
-#pragma unroll
-            for (int t = 0; t < NT; ++t) af[t] = *(const half8_t *)(qb + (0 * QROWS + t * 32) * BX_PITCH + sstep * 8);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t], xl, acc[t], 0, 0, 0);      // qh xl
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t], xh, acc[t], 0, 0, 0);      // qh xh
-        }
-        if (c + 1 < nchunks) store_q(buf ^ 1);
-        __syncthreads();
-    }
-    if (row < n_rows) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int q = q0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                if (q < q_valid) sims[(int64_t)q * sims_stride + row] = acc[t][r] * rsc.y;
-            }
-    }
 }
 
 __device__ __forceinline__ uint32_t float_desc_key(float f)
@@ -605,60 +98,83 @@ __global__ __launch_bounds__(TPB) void k_name_rank(int n_cand, const uint32_t *_
     rank[sorted_vals[i]] = (uint32_t)i;
 }
 
-struct CandArgs {
-    int n_cand, max_id, vcap, cache_size, exact, use_radius, c0, c1, c2, floor_lo, floor_hi;
-    double radius2;
+// ---- the candidates of the selection ------------------------------------------------------------------------------------------
+// The store as the candidate kernels read it, whatever its mode.  Candidate (voxel) c in [0, max_id] sits in entry c of cnt /
+// rgb_pos / store_rows, except c == max_id, the grid_0_0_0 group: entry vcap, position (0, 0, 0).  (Dense acnt has no slot of its
+// own for that group: it is allocated vcap + 1.)
+struct VoxelView {
+    int max_id, vcap, cache_size, exact;
     const int32_t *rgb_pos, *cnt, *store_rows;
     const uint32_t *name_rank;
+
+    __device__ __forceinline__ int entry(int c) const { return (c == max_id) ? vcap : c; }
+    __device__ __forceinline__ void position(int c, int &r, int &cc, int &h) const
+    {
+        r = 0; cc = 0; h = 0;
+        if (c != max_id) { r = rgb_pos[3 * c]; cc = rgb_pos[3 * c + 1]; h = rgb_pos[3 * c + 2]; }
+    }
+    // similarity key of the best of the m tokens of entry e (memory_2.py:661) when the scan ran over the store's own rows: token-pool
+    // rows of an exact store, row e of a dense map
+    __device__ __forceinline__ float best_sim(int e, int m, const float *__restrict__ sims) const
+    {
+        if (!exact) return sims[e];
+        float best = -INFINITY;
+        for (int k = 0; k < m; ++k) best = fmaxf(best, sims[store_rows[(int64_t)e * cache_size + k]]);
+        return best;
+    }
 };
 
-// similarity part of the rank key of candidate c for one query (0xffffffff: filtered out / empty):
-// region / floor filters, max over the voxel's tokens
-__device__ __forceinline__ uint32_t cand_simkey(const CandArgs &a, int c, const float *__restrict__ sims)
+// what the context's store holds now (read_scalars first): the view, and through the pointers the candidates (max_id + 1) and the
+// matrix the scan reads
+static VoxelView store_view(const bsc_ctx *x, int *n_cand, int64_t *n_rows, const float **rows)
 {
-    if (c >= a.n_cand) return 0xffffffffu;
-    const int e = (c == a.max_id) ? a.vcap : c;
-    const int m = a.cnt[e];
-    if (m <= 0) return 0xffffffffu;
-    if (a.use_radius || a.floor_lo <= a.floor_hi) {
-        int r = 0, cc = 0, h = 0;
-        if (c != a.max_id) { r = a.rgb_pos[3 * e]; cc = a.rgb_pos[3 * e + 1]; h = a.rgb_pos[3 * e + 2]; }
-        if (a.use_radius) {   // memory_2.py:624-629 (integer squared distance compared with radius**2)
-            const double dx = r - a.c0, dy = cc - a.c1, dz = h - a.c2;
-            if (!((dx * dx + dy * dy + dz * dz) <= a.radius2)) return 0xffffffffu;
-        }
-        if (a.floor_lo <= a.floor_hi && !((a.floor_lo <= h) && (h <= a.floor_hi))) return 0xffffffffu;   // :633-640
-    }
-    float best = -INFINITY;
-    if (a.exact) {
-        for (int k = 0; k < m; ++k) best = fmaxf(best, sims[a.store_rows[(int64_t)e * a.cache_size + k]]);   // :661
-    } else {
-        best = sims[e];
-    }
-    const uint32_t sk = float_desc_key(best);
-    return sk == 0xffffffffu ? 0xfffffffeu : sk;     // keep the all-ones pattern for "no candidate"
+    const bool exact = x->c.mode == BSC_MODE_EXACT;
+    VoxelView v;
+    v.max_id = (int)x->hscal[DS_MAX_ID]; v.vcap = x->c.voxel_capacity; v.cache_size = x->c.cache_size; v.exact = exact ? 1 : 0;
+    v.rgb_pos = x->rgb_pos; v.cnt = exact ? x->store_cnt : x->acnt; v.store_rows = x->store_rows; v.name_rank = x->l_name_rank;
+    *n_cand = v.max_id + 1;
+    *n_rows = exact ? x->hscal[DS_POOL_N] : v.max_id;
+    *rows = exact ? x->pool : x->acc;
+    return v;
 }
 
-// The selection kernels below are written once for two kinds of candidate list: CandArgs (bsc_localize: every voxel, one region
-// for all queries) and RegionCandArgs (bsc_localize_regions: a region per query, possibly a compacted list).  Entry i of a list
-// has a similarity key for query q, a voxel (what k_gather_topk reads the position of) and a name rank.
-__device__ __forceinline__ uint32_t cand_simkey(const CandArgs &a, int c, int, const float *__restrict__ sims) { return cand_simkey(a, c, sims); }
-__device__ __forceinline__ uint32_t cand_val(const CandArgs &, int c) { return (uint32_t)c; }
-__device__ __forceinline__ uint32_t cand_rank(const CandArgs &a, int c) { return a.name_rank[c]; }
-
-// ---- a region per query (bsc_localize_regions) ---------------------------------------------------------------------------
-// bsc_region as the kernels read it: radius^2 in double like CandArgs::radius2, the two switches resolved
+// bsc_region as the kernels read it: radius^2 in double, the two switches resolved
 struct RegionDev {
     double radius2;
     int32_t c0, c1, c2, floor_lo, floor_hi, use_radius;
 };
 static_assert(sizeof(RegionDev) == 32, "RegionDev layout");
 
-struct RegionCandArgs {
+static RegionDev region_dev(double radius, const int32_t *curr, int32_t floor_lo, int32_t floor_hi)
+{
+    return RegionDev{radius * radius, curr ? curr[0] : 0, curr ? curr[1] : 0, curr ? curr[2] : 0, floor_lo, floor_hi, radius >= 0 ? 1 : 0};
+}
+
+// neither sphere nor floor band: the region holds every voxel
+__host__ __device__ static inline bool region_open(const RegionDev &g) { return !g.use_radius && !(g.floor_lo <= g.floor_hi); }
+
+// memory_2.py:624-640 for one voxel and one region
+__device__ __forceinline__ bool region_sees(const RegionDev &g, int r, int cc, int h)
+{
+    if (g.use_radius) {   // :624-629 (integer squared distance compared with radius**2)
+        const double dx = r - g.c0, dy = cc - g.c1, dz = h - g.c2;
+        if (!((dx * dx + dy * dy + dz * dz) <= g.radius2)) return false;
+    }
+    if (g.floor_lo <= g.floor_hi && !((g.floor_lo <= h) && (h <= g.floor_hi))) return false;   // :633-640
+    return true;
+}
+
+// The selection kernels below are written once for two kinds of candidate list: CandArgs (bsc_localize: every voxel, one region
+// for all queries) and RegionCandArgs (bsc_localize_regions: a region per query, possibly a compacted list).  Entry i of a list
+// has a similarity key for query q (0xffffffff: filtered out / empty), a voxel (what k_gather_topk reads the position of) and a
+// name rank.
+struct CandArgs : VoxelView {
+    int n_cand;                    // max_id + 1
+    RegionDev region;
+};
+
+struct RegionCandArgs : VoxelView {
     int n_cand;                    // entries of the list: max_id + 1, or the visible voxels when the scan was pruned
-    int max_id, vcap, cache_size, exact;
-    const int32_t *rgb_pos, *cnt, *store_rows;
-    const uint32_t *name_rank;
     const RegionDev *regions;      // (Q)
     const uint32_t *mask;          // visibility bits, word (q / 32) * mask_stride + voxel; nullptr: the pass was skipped
     int64_t mask_stride;
@@ -666,15 +182,30 @@ struct RegionCandArgs {
     const int32_t *rowoff;         // pruned scan: entry -> its first row in the gathered matrix
 };
 
-// memory_2.py:624-640 for one voxel and one region: the test of cand_simkey
-__device__ __forceinline__ bool region_sees(const RegionDev &g, int r, int cc, int h)
+static CandArgs cand_args(const VoxelView &v, int n_cand, const RegionDev &region) { return CandArgs{v, n_cand, region}; }
+// every voxel for every query
+static CandArgs cand_args_open(const VoxelView &v, int n_cand) { return cand_args(v, n_cand, region_dev(-1.0, nullptr, 0, -1)); }
+
+__device__ __forceinline__ uint32_t simkey_of(float best)
 {
-    if (g.use_radius) {
-        const double dx = r - g.c0, dy = cc - g.c1, dz = h - g.c2;
-        if (!((dx * dx + dy * dy + dz * dz) <= g.radius2)) return false;
+    const uint32_t sk = float_desc_key(best);
+    return sk == 0xffffffffu ? 0xfffffffeu : sk;     // keep the all-ones pattern for "no candidate"
+}
+
+__device__ __forceinline__ uint32_t cand_val(const CandArgs &, int c) { return (uint32_t)c; }
+__device__ __forceinline__ uint32_t cand_rank(const CandArgs &a, int c) { return a.name_rank[c]; }
+__device__ __forceinline__ uint32_t cand_simkey(const CandArgs &a, int c, int, const float *__restrict__ sims)
+{
+    if (c >= a.n_cand) return 0xffffffffu;
+    const int e = a.entry(c);
+    const int m = a.cnt[e];
+    if (m <= 0) return 0xffffffffu;
+    if (!region_open(a.region)) {
+        int r, cc, h;
+        a.position(c, r, cc, h);
+        if (!region_sees(a.region, r, cc, h)) return 0xffffffffu;
     }
-    if (g.floor_lo <= g.floor_hi && !((g.floor_lo <= h) && (h <= g.floor_hi))) return false;
-    return true;
+    return simkey_of(a.best_sim(e, m, sims));
 }
 
 __device__ __forceinline__ uint32_t cand_val(const RegionCandArgs &a, int i) { return a.cidx ? (i < a.n_cand ? a.cidx[i] : 0u) : (uint32_t)i; }
@@ -683,27 +214,21 @@ __device__ __forceinline__ uint32_t cand_simkey(const RegionCandArgs &a, int i, 
 {
     if (i >= a.n_cand) return 0xffffffffu;
     const int c = (int)cand_val(a, i);
-    const int e = (c == a.max_id) ? a.vcap : c;
+    const int e = a.entry(c);
     const int m = a.cnt[e];
     if (a.mask) {                  // the visibility pass made the test (empty voxels see nothing there)
         if (!((a.mask[(int64_t)(q >> 5) * a.mask_stride + c] >> (q & 31)) & 1u)) return 0xffffffffu;
     } else {
         if (m <= 0) return 0xffffffffu;
-        int r = 0, cc = 0, h = 0;
-        if (c != a.max_id) { r = a.rgb_pos[3 * e]; cc = a.rgb_pos[3 * e + 1]; h = a.rgb_pos[3 * e + 2]; }
+        int r, cc, h;
+        a.position(c, r, cc, h);
         if (!region_sees(a.regions[q], r, cc, h)) return 0xffffffffu;
     }
-    float best = -INFINITY;
-    if (a.rowoff) {                // gathered rows of entry i are consecutive
-        const int base = a.rowoff[i], nr = a.exact ? m : 1;
-        for (int k = 0; k < nr; ++k) best = fmaxf(best, sims[base + k]);
-    } else if (a.exact) {
-        for (int k = 0; k < m; ++k) best = fmaxf(best, sims[a.store_rows[(int64_t)e * a.cache_size + k]]);
-    } else {
-        best = sims[e];
-    }
-    const uint32_t sk = float_desc_key(best);
-    return sk == 0xffffffffu ? 0xfffffffeu : sk;
+    if (!a.rowoff) return simkey_of(a.best_sim(e, m, sims));
+    float best = -INFINITY;        // gathered rows of entry i are consecutive
+    const int base = a.rowoff[i], nr = a.exact ? m : 1;
+    for (int k = 0; k < nr; ++k) best = fmaxf(best, sims[base + k]);
+    return simkey_of(best);
 }
 
 // full rank key: similarity descending, ties in HDF5 name order
@@ -832,6 +357,20 @@ __device__ __forceinline__ void bitonic_1024_regs(u64 (&key)[4], uint32_t (&val)
     }
 }
 
+// the K smallest of a sorted slice (element 256 r + tid in slot r) -> the K winner slots at out_keys / out_vals
+__device__ __forceinline__ void store_winners(const u64 (&key)[4], const uint32_t (&val)[4], int K, u64 *__restrict__ out_keys,
+                                              uint32_t *__restrict__ out_vals)
+{
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int e = r * 256 + (int)threadIdx.x;
+        if (e < K) {
+            out_keys[e] = key[r];
+            out_vals[e] = val[r];
+        }
+    }
+}
+
 // first round, fused with the candidate scan: block (b, q) ranks candidates [1024 b, 1024 b + 1024) of query q
 template <class A>
 __global__ __launch_bounds__(TPB) void k_cand_topk(A a, const float *__restrict__ sims, int64_t sims_stride, int K,
@@ -853,14 +392,7 @@ __global__ __launch_bounds__(TPB) void k_cand_topk(A a, const float *__restrict_
         }
         __syncthreads();                                            // the previous item's partner reads are done
         bitonic_1024_regs(key, val, bk, bv);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int e = r * 256 + (int)threadIdx.x;
-            if (e < K) {
-                out_keys[(int64_t)q * out_stride + (int64_t)bx * K + e] = key[r];
-                out_vals[(int64_t)q * out_stride + (int64_t)bx * K + e] = val[r];
-            }
-        }
+        store_winners(key, val, K, out_keys + (int64_t)q * out_stride + (int64_t)bx * K, out_vals + (int64_t)q * out_stride + (int64_t)bx * K);
     }
 }
 
@@ -897,14 +429,7 @@ __global__ __launch_bounds__(TPB) void k_block_topk(const u64 *__restrict__ in_k
         }
         __syncthreads();
         bitonic_1024_regs(key, val, bk, bv);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int e = r * 256 + (int)threadIdx.x;
-            if (e < K) {
-                out_keys[(int64_t)q * out_stride + (int64_t)bx * K + e] = key[r];
-                out_vals[(int64_t)q * out_stride + (int64_t)bx * K + e] = val[r];
-            }
-        }
+        store_winners(key, val, K, out_keys + (int64_t)q * out_stride + (int64_t)bx * K, out_vals + (int64_t)q * out_stride + (int64_t)bx * K);
     }
 }
 
@@ -1032,7 +557,7 @@ __global__ void k_sel_check(const u64 *__restrict__ thr, const int32_t *__restri
 #endif
 }
 
-static bsc_status grow_dev(void **p, int64_t *cap, int64_t need_bytes)
+bsc_status grow_dev(void **p, int64_t *cap, int64_t need_bytes)
 {
     if (*cap >= need_bytes) return BSC_OK;
     if (*p) (void)hipFree(*p);
@@ -1113,7 +638,7 @@ static bsc_status select_topk_batched(bsc_ctx *x, const A &ca, int nq, int64_t s
         // dense maps without region / floor filter: candidate c is row c, similarities stream as 16-byte loads
         bool fast = false;
         if constexpr (std::is_same<A, CandArgs>::value)
-            fast = !ca.exact && !ca.use_radius && !(ca.floor_lo <= ca.floor_hi) && (sims_stride % 4 == 0);
+            fast = !ca.exact && region_open(ca.region) && (sims_stride % 4 == 0);
         const dim3 fgrid(nbf * (unsigned)nq < 16384u ? nbf * (unsigned)nq : 16384u);
         if constexpr (std::is_same<A, CandArgs>::value) {
           if (fast)
@@ -1142,128 +667,16 @@ bsc_status pool_query_impl(bsc_ctx *x, const float *tokens, int32_t B, int32_t T
     return BSC_OK;
 }
 
-// similarity rows of consecutive queries must not sit a power of two apart: a 2^22-byte stride puts the rows that
-// are read concurrently (8+ queries in flight) on the same HBM channel / bank set and the candidate passes drop to
-// 0.4 TB/s.  Rows are padded to a multiple of 64 floats plus an odd number of 256-byte units.
-int64_t sims_row_stride(int64_t n_rows) { return ((n_rows + 63) & ~(int64_t)63) + 64 * 33; }
-
-template <int QT>
-static void launch_cosine(bsc_ctx *x, const float *rows, int64_t n_rows, int q0)
+// name ranks (HDF5 iteration order) are rebuilt only when the set of stored voxels changed
+static bsc_status ensure_name_ranks(bsc_ctx *x, const VoxelView &v)
 {
-    const int D = x->c.token_dim;
-    const int nv = (D / 4 + 63) / 64;
-    int64_t blocks = (n_rows * 64 + TPB - 1) / TPB;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    if (blocks < 1) blocks = 1;
-    const dim3 grid((unsigned)blocks), block(TPB);
-#define LC(NV) hipLaunchKernelGGL((k_cosine<NV, QT>), grid, block, 0, x->stream, rows, n_rows, D, x->l_q, q0, x->l_sims, sims_row_stride(n_rows))
-    if (nv <= 1) LC(1);
-    else if (nv == 2) LC(2);
-    else if (nv == 3) LC(3);
-    else if (nv == 4) LC(4);
-    else LC(8);
-#undef LC
-}
-
-// The cosine scan of nq normalised queries (x->l_q) over the matrix rows (n_rows, D) -> x->l_sims, query rows sims_row_stride(n_rows)
-// apart.  rs / rs_cap / rs_dirty: the cached per-row scales of THESE rows for the fp16-piece scan (the context's own for its store,
-// a scratch set for a gathered matrix).  *passes_out = times the matrix was streamed.
-static bsc_status cosine_scan(bsc_ctx *x, const float *rows, int64_t n_rows, int nq, float2 **rs, int64_t *rs_cap, bool *rs_dirty,
-                              int *passes_out)
-{
-    hipStream_t s = x->stream;
-    const int D = x->c.token_dim;
-    const dim3 block(TPB);
-    int done = 0;
-    const int64_t sstride = sims_row_stride(n_rows);
-    int passes = 0;                          // times the row matrix is streamed
-    if (nq >= BSC_MFMA_MIN_Q && D % MF_KC == 0 && n_rows > 0) {
-        // batched queries on the matrix cores, 32-query tiles (l_q is zero-padded to a multiple of 256 rows): more than 32
-        // 64 queries -> bf16 pieces at f32 accuracy (k_cosine_bf16x3); up to 64 -> the f32 MFMA, HBM-bound at that size anyway
-        const dim3 mgrid((unsigned)((n_rows + 127) / 128));
-        static const bool f32_only = getenv("BSC_COSINE_F32") != nullptr;
-        // six piece products (f32 accuracy, the default) or BSC_COSINE_PIECES=3 (hh, hm, mh): 0.7x the scan time, scores within
-        // ~4e-6 instead of 3e-7 — enough for the north star's 1e-3, not for the 2e-6 the fp64 parity tests ask; read per call
-        const char *pcs = getenv("BSC_COSINE_PIECES");
-        const bool six = !(pcs && atoi(pcs) == 3);
-        static const bool wv8 = getenv("BSC_COSINE_WV4") == nullptr;                     // A/B: 8 (default) or 4 wavefronts per workgroup                 // A/B: the round-2 f32 MFMA scan throughout
-        const int padded = ((nq + 255) / 256) * 256 > 1024 ? 1024 : ((nq + 255) / 256) * 256;
-        const bool bf16_pieces = getenv("BSC_COSINE_BF16") != nullptr;                 // A/B (read per call): the round-3/4 six-product bf16 scan
-        if (!f32_only && nq > 64 && !bf16_pieces) {
-            // fp16 pieces, three products (round 5): per-row scales / inverse norms cached until the rows change
-            const int64_t nel = (int64_t)padded * D;
-            if (*rs_dirty || !*rs || *rs_cap < (int64_t)sizeof(float2) * n_rows) {
-                if (*rs_cap < (int64_t)sizeof(float2) * n_rows)
-                    BSC_TRY(grow_dev((void **)rs, rs_cap, sizeof(float2) * (n_rows + n_rows / 8 + 1024)));
-                hipLaunchKernelGGL(k_row_scale, dim3((unsigned)((n_rows * 64 + TPB - 1) / TPB)), block, 0, s, rows, n_rows, D, *rs);
-                *rs_dirty = false;
-            }
-            hipLaunchKernelGGL(k_split_q_f16, dim3((unsigned)((nel / 2 + TPB - 1) / TPB)), block, 0, s, x->l_q, nel, x->l_qp);
-            while (done < nq) {
-                const int left = nq - done;
-                ++passes;
-#define FX_LAUNCH(NTV, ADV)                                                                                                         \
-    do {                                                                                                                            \
-        const size_t lds = (size_t)2 * 2 * (NTV * 32) * BX_PITCH * sizeof(uint16_t);                                               \
-        (void)hipFuncSetAttribute((const void *)k_cosine_f16x2<NTV, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-        hipLaunchKernelGGL((k_cosine_f16x2<NTV, 8>), dim3((unsigned)((n_rows + 255) / 256)), dim3(512), lds, s, rows, n_rows, D,    \
-                           (const uint16_t *)x->l_qp, nel, done, nq, (const float2 *)*rs, x->l_sims, sstride);              \
-        done += ADV;                                                                                                                \
-    } while (0)
-                if (left > 128) FX_LAUNCH(8, 256);
-                else if (left > 64) FX_LAUNCH(4, 128);
-                else { --passes; break; }                    // the remainder (<= 64 queries) goes to the f32 MFMA below
-#undef FX_LAUNCH
-            }
-        } else if (!f32_only && nq > 64) {         // measured over 2^20 x 768: 33..64 queries 1.17-1.28 ms against 1.09 ms on the f32 MFMA (HBM-bound either way)
-            const int64_t nel = (int64_t)padded * D;
-            hipLaunchKernelGGL(k_split_q, dim3((unsigned)((nel / 2 + TPB - 1) / TPB)), block, 0, s, x->l_q, nel, x->l_qp);
-            // k_split_q wrote planes nel apart; the scan indexes them with the same stride
-            while (done < nq) {
-                const int left = nq - done;
-                ++passes;
-#define BX_LAUNCH2(NTV, WVV, SIXV, GRID, BLOCK)                                                                                     \
-    do {                                                                                                                            \
-        (void)hipFuncSetAttribute((const void *)k_cosine_bf16x3<NTV, WVV, SIXV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_cosine_bf16x3<NTV, WVV, SIXV>), GRID, BLOCK, lds, s, rows, n_rows, D, (const uint16_t *)x->l_qp, nel,  \
-                           done, nq, x->l_sims, sstride);                                                                           \
-    } while (0)
-#define BX_LAUNCH(NTV, ADV)                                                                                                        \
-    do {                                                                                                                            \
-        const size_t lds = (size_t)2 * 3 * (NTV * 32) * BX_PITCH * sizeof(uint16_t);                                               \
-        const dim3 g8((unsigned)((n_rows + 255) / 256)), b8(512);                                                                   \
-        if (wv8 && six) BX_LAUNCH2(NTV, 8, true, g8, b8);                                                                           \
-        else if (wv8) BX_LAUNCH2(NTV, 8, false, g8, b8);                                                                            \
-        else if (six) BX_LAUNCH2(NTV, 4, true, mgrid, block);                                                                       \
-        else BX_LAUNCH2(NTV, 4, false, mgrid, block);                                                                               \
-        done += ADV;                                                                                                                \
-    } while (0)
-                if (left > 128) BX_LAUNCH(8, 256);
-                else if (left > 64) BX_LAUNCH(4, 128);
-                else { --passes; break; }                    // the remainder (<= 64 queries) goes to the f32 MFMA below
-#undef BX_LAUNCH
-#undef BX_LAUNCH2
-            }
-        }
-        while (done < nq) {
-            const int left = nq - done;
-            ++passes;
-            if (left > 128) { hipLaunchKernelGGL((k_cosine_mfma<8>), mgrid, block, 0, s, rows, n_rows, D, x->l_q, done, nq, x->l_sims, sstride); done += 256; }
-            else if (left > 64) { hipLaunchKernelGGL((k_cosine_mfma<4>), mgrid, block, 0, s, rows, n_rows, D, x->l_q, done, nq, x->l_sims, sstride); done += 128; }
-            else if (left > 32) { hipLaunchKernelGGL((k_cosine_mfma<2>), mgrid, block, 0, s, rows, n_rows, D, x->l_q, done, nq, x->l_sims, sstride); done += 64; }
-            else { hipLaunchKernelGGL((k_cosine_mfma<1>), mgrid, block, 0, s, rows, n_rows, D, x->l_q, done, nq, x->l_sims, sstride); done += 32; }
-        }
-        done = nq;
-    }
-    while (done < nq && n_rows > 0) {      // the row matrix is streamed once per group of up to 8 queries
-        const int left = nq - done;
-        ++passes;
-        if (left >= 8) { launch_cosine<8>(x, rows, n_rows, done); done += 8; }
-        else if (left >= 4) { launch_cosine<4>(x, rows, n_rows, done); done += 4; }
-        else if (left >= 2) { launch_cosine<2>(x, rows, n_rows, done); done += 2; }
-        else { launch_cosine<1>(x, rows, n_rows, done); done += 1; }
-    }
-    *passes_out = passes;
+    if (!x->names_dirty) return BSC_OK;
+    const int n_cand = v.max_id + 1;
+    const dim3 block(TPB), cgrid((n_cand + TPB - 1) / TPB);
+    hipLaunchKernelGGL(k_name_keys, cgrid, block, 0, x->stream, n_cand, v.max_id, v.vcap, v.rgb_pos, v.cnt, x->l_key_a, x->l_val_a);
+    BSC_TRY(prim_sort_pairs(x, x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b, (size_t)n_cand, 0, 64));
+    hipLaunchKernelGGL(k_name_rank, cgrid, block, 0, x->stream, n_cand, x->l_val_b, x->l_name_rank);
+    x->names_dirty = false;
     return BSC_OK;
 }
 
@@ -1274,26 +687,26 @@ static bsc_status cosine_scan(bsc_ctx *x, const float *rows, int64_t n_rows, int
 void localize_prepare(bsc_ctx *x)
 {
     if (read_scalars(x) != BSC_OK) return;
-    hipStream_t s = x->stream;
-    const bool exact = x->c.mode == BSC_MODE_EXACT;
-    const int max_id = (int)x->hscal[DS_MAX_ID], vcap = x->c.voxel_capacity, n_cand = max_id + 1, D = x->c.token_dim;
-    const int64_t n_rows = exact ? x->hscal[DS_POOL_N] : max_id;
-    const float *rows = exact ? x->pool : x->acc;
-    const int32_t *cnt = exact ? x->store_cnt : x->acnt;
-    const dim3 block(TPB), cgrid((n_cand + TPB - 1) / TPB);
-    if (x->names_dirty && max_id > 0) {
-        hipLaunchKernelGGL(k_name_keys, cgrid, block, 0, s, n_cand, max_id, vcap, x->rgb_pos, cnt, x->l_key_a, x->l_val_a);
-        if (prim_sort_pairs(x, x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b, (size_t)n_cand, 0, 64) != BSC_OK) return;
-        hipLaunchKernelGGL(k_name_rank, cgrid, block, 0, s, n_cand, x->l_val_b, x->l_name_rank);
-        x->names_dirty = false;
-    }
-    if (x->row_scale_dirty && n_rows > 0 && D % MF_KC == 0) {
-        if (x->l_rscale_cap < (int64_t)sizeof(float2) * n_rows &&
-            grow_dev((void **)&x->l_rscale, &x->l_rscale_cap, sizeof(float2) * (n_rows + n_rows / 8 + 1024)) != BSC_OK) return;
-        hipLaunchKernelGGL(k_row_scale, dim3((unsigned)((n_rows * 64 + TPB - 1) / TPB)), block, 0, s, rows, n_rows, D, x->l_rscale);
-        x->row_scale_dirty = false;
-    }
+    int n_cand;
+    int64_t n_rows;
+    const float *rows;
+    const VoxelView v = store_view(x, &n_cand, &n_rows, &rows);
+    if (v.max_id > 0 && ensure_name_ranks(x, v) != BSC_OK) return;
+    if (x->row_scale_dirty && refresh_row_scales(x, rows, n_rows, &x->l_rscale, &x->l_rscale_cap, &x->row_scale_dirty) != BSC_OK) return;
     (void)hipGetLastError();
+}
+
+// the counts the callers get (entries of a query's K with a position) and the shape of the results that stay resident
+static void record_counts(bsc_ctx *x, int nq, int K, const int32_t *out_pos, int32_t *out_count)
+{
+    for (int qi = 0; qi < nq; ++qi) {
+        int n = 0;
+        while (n < K && out_pos[((int64_t)qi * K + n) * 3] >= 0) ++n;
+        out_count[qi] = n;
+        x->last_counts[qi] = n;
+    }
+    x->last_nq = nq;
+    x->last_K = K;
 }
 
 // top-K of every query from its similarities (x->l_sims, rows sstride apart) -> x->l_out_pos / l_out_sim (they stay resident as the
@@ -1335,60 +748,30 @@ static bsc_status select_and_copy_out(bsc_ctx *x, const A &ca, int nq, int K, in
     BSC_HIP(hipMemcpyAsync(out_pos, x->l_out_pos, sizeof(int32_t) * (size_t)nq * K * 3, hipMemcpyDeviceToHost, s));
     BSC_HIP(hipMemcpyAsync(out_sim, x->l_out_sim, sizeof(float) * (size_t)nq * K, hipMemcpyDeviceToHost, s));
     BSC_HIP(hipStreamSynchronize(s));
-    for (int qi = 0; qi < nq; ++qi) {
-        int n = 0;
-        while (n < K && out_pos[((int64_t)qi * K + n) * 3] >= 0) ++n;
-        out_count[qi] = n;
-        x->last_counts[qi] = n;
-    }
-    x->last_nq = nq;
-    x->last_K = K;
+    record_counts(x, nq, K, out_pos, out_count);
     return BSC_OK;
 }
 
 bsc_status localize_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, double radius, const int32_t *curr,
                          int32_t floor_lo, int32_t floor_hi, int32_t *out_pos, float *out_sim, int32_t *out_count)
 {
-    hipStream_t s = x->stream;
-    const int D = x->c.token_dim;
-    const bool exact = x->c.mode == BSC_MODE_EXACT;
     BSC_TRY(read_scalars(x));
-    const int max_id = (int)x->hscal[DS_MAX_ID];
-    const int vcap = x->c.voxel_capacity;
-    const int n_cand = max_id + 1;
-    const int64_t n_rows = exact ? x->hscal[DS_POOL_N] : max_id;
-    const float *rows = exact ? x->pool : x->acc;
-    const int32_t *cnt = exact ? x->store_cnt : x->acnt;
-    const dim3 block(TPB), cgrid((n_cand + TPB - 1) / TPB);
+    int n_cand;
+    int64_t n_rows;
+    const float *rows;
+    const VoxelView v = store_view(x, &n_cand, &n_rows, &rows);
     if (K > 4096 || K < 1 || nq < 1 || nq > 1024) {
         bsc_set_error("bsc_localize: K=%d (1..4096), n_queries=%d (1..1024)", K, nq);
         return BSC_E_INVALID;
     }
-    // name ranks (HDF5 iteration order) are rebuilt only when the set of stored voxels changed
-    if (x->names_dirty) {
-        hipLaunchKernelGGL(k_name_keys, cgrid, block, 0, s, n_cand, max_id, vcap, x->rgb_pos, cnt, x->l_key_a, x->l_val_a);
-        BSC_TRY(prim_sort_pairs(x, x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b, (size_t)n_cand, 0, 64));
-        hipLaunchKernelGGL(k_name_rank, cgrid, block, 0, s, n_cand, x->l_val_b, x->l_name_rank);
-        x->names_dirty = false;
-    }
-    {   // the MFMA path reads whole query tiles: zero-pad up to the next multiple of 256 (l_q holds 1024 rows)
-        const int padded = ((nq + 255) / 256) * 256;
-        BSC_HIP(hipMemsetAsync(x->l_q, 0, sizeof(float) * (size_t)(padded > 1024 ? 1024 : padded) * D, s));
-    }
-    hipLaunchKernelGGL(k_normalize_q, dim3(nq), dim3(64), 0, s, q_dev, D, x->l_q);
-    // dense acnt has no slot for the grid_0_0_0 group: k_candidates reads cnt[vcap]; acnt is allocated vcap+1
+    BSC_TRY(ensure_name_ranks(x, v));
+    BSC_TRY(stage_queries(x, q_dev, nq));
     stat_begin(x, 1);
-    const int64_t sstride = sims_row_stride(n_rows);
     int passes = 0;                          // times the row matrix is streamed
     BSC_TRY(cosine_scan(x, rows, n_rows, nq, &x->l_rscale, &x->l_rscale_cap, &x->row_scale_dirty, &passes));
-    stat_end(x, 1, (double)n_rows * D * 4.0 * passes + (double)nq * n_rows * 4.0);
-    CandArgs ca;
-    ca.n_cand = n_cand; ca.max_id = max_id; ca.vcap = vcap; ca.cache_size = x->c.cache_size; ca.exact = exact ? 1 : 0;
-    ca.use_radius = radius >= 0 ? 1 : 0;
-    ca.c0 = curr ? curr[0] : 0; ca.c1 = curr ? curr[1] : 0; ca.c2 = curr ? curr[2] : 0;
-    ca.floor_lo = floor_lo; ca.floor_hi = floor_hi; ca.radius2 = radius * radius;
-    ca.rgb_pos = x->rgb_pos; ca.cnt = cnt; ca.store_rows = x->store_rows; ca.name_rank = x->l_name_rank;
-    return select_and_copy_out(x, ca, nq, K, sstride, /*strict*/ 1, out_pos, out_sim, out_count);
+    stat_end(x, 1, (double)n_rows * x->c.token_dim * 4.0 * passes + (double)nq * n_rows * 4.0);
+    return select_and_copy_out(x, cand_args(v, n_cand, region_dev(radius, curr, floor_lo, floor_hi)), nq, K, sims_row_stride(n_rows),
+                               /*strict*/ 1, out_pos, out_sim, out_count);
 }
 
 // ---- bsc_localize_regions: a sphere and a floor band per query, pruned scan ---------------------------------------------
@@ -1555,38 +938,22 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
 {
     hipStream_t s = x->stream;
     const int D = x->c.token_dim;
-    const bool exact = x->c.mode == BSC_MODE_EXACT;
+    const dim3 block(TPB);
     RegionWs *w;
     BSC_TRY(region_ws_get(x, &w));
     BSC_TRY(read_scalars(x));
-    const int max_id = (int)x->hscal[DS_MAX_ID];
-    const int vcap = x->c.voxel_capacity;
-    const int n_cand = max_id + 1;
-    const int64_t n_rows = exact ? x->hscal[DS_POOL_N] : max_id;
-    const float *rows = exact ? x->pool : x->acc;
-    const int32_t *cnt = exact ? x->store_cnt : x->acnt;
-    const dim3 block(TPB), cgrid((n_cand + TPB - 1) / TPB);
-    if (x->names_dirty) {
-        hipLaunchKernelGGL(k_name_keys, cgrid, block, 0, s, n_cand, max_id, vcap, x->rgb_pos, cnt, x->l_key_a, x->l_val_a);
-        BSC_TRY(prim_sort_pairs(x, x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b, (size_t)n_cand, 0, 64));
-        hipLaunchKernelGGL(k_name_rank, cgrid, block, 0, s, n_cand, x->l_val_b, x->l_name_rank);
-        x->names_dirty = false;
-    }
-    {
-        const int padded = ((nq + 255) / 256) * 256;
-        BSC_HIP(hipMemsetAsync(x->l_q, 0, sizeof(float) * (size_t)(padded > 1024 ? 1024 : padded) * D, s));
-    }
-    hipLaunchKernelGGL(k_normalize_q, dim3(nq), dim3(64), 0, s, q_dev, D, x->l_q);
+    int n_cand;
+    int64_t n_rows;
+    const float *rows;
+    const VoxelView v = store_view(x, &n_cand, &n_rows, &rows);
+    BSC_TRY(ensure_name_ranks(x, v));
+    BSC_TRY(stage_queries(x, q_dev, nq));
     // the regions as the kernels read them; a query with neither sphere nor band sees every voxel
     bool any_open = false, all_open = true;
     for (int qi = 0; qi < nq; ++qi) {
         const bsc_region &g = regions[qi];
-        RegionDev &d = w->regions_pin[qi];
-        d.use_radius = g.radius >= 0 ? 1 : 0;
-        d.radius2 = g.radius * g.radius;
-        d.c0 = g.curr[0]; d.c1 = g.curr[1]; d.c2 = g.curr[2];
-        d.floor_lo = g.floor_lo; d.floor_hi = g.floor_hi;
-        if (!d.use_radius && !(d.floor_lo <= d.floor_hi)) any_open = true;
+        w->regions_pin[qi] = region_dev(g.radius, g.curr, g.floor_lo, g.floor_hi);
+        if (region_open(w->regions_pin[qi])) any_open = true;
         else all_open = false;
     }
     BSC_HIP(hipMemcpyAsync(w->regions, w->regions_pin, sizeof(RegionDev) * (size_t)nq, hipMemcpyHostToDevice, s));
@@ -1614,7 +981,7 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
             BSC_TRY(grow_dev((void **)&w->blk_off, &w->blk_cap[1], sizeof(int64_t) * (nblk + nblk / 8 + 64)));
         }
         BSC_HIP(hipMemsetAsync(w->blk_tot + nblk, 0, sizeof(int64_t), s));           // the scan's last output is the total
-        hipLaunchKernelGGL(k_region_visibility, dim3(nblk), block, 0, s, n_cand, max_id, vcap, exact ? 1 : 0, x->rgb_pos, cnt,
+        hipLaunchKernelGGL(k_region_visibility, dim3(nblk), block, 0, s, n_cand, v.max_id, v.vcap, v.exact, v.rgb_pos, v.cnt,
                            (const RegionDev *)w->regions, nq, w->mask, mask_stride, w->vis, w->blk_tot);
         if (!never) {
             BSC_TRY(prim_exclusive_sum_i64(x, w->blk_tot, w->blk_off, (size_t)nblk + 1));
@@ -1631,9 +998,7 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
         BSC_HIP(hipGetLastError());
         BSC_HIP(hipStreamSynchronize(s));
         for (int64_t i = 0; i < (int64_t)nq * K; ++i) { out_pos[3 * i] = out_pos[3 * i + 1] = out_pos[3 * i + 2] = -1; out_sim[i] = -INFINITY; }
-        for (int qi = 0; qi < nq; ++qi) { out_count[qi] = 0; x->last_counts[qi] = 0; }
-        x->last_nq = nq;
-        x->last_K = K;
+        record_counts(x, nq, K, out_pos, out_count);      // all zero
         return BSC_OK;
     }
     const float *scan_rows = rows;
@@ -1648,11 +1013,11 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
         }
         if (w->rows_cap < (int64_t)sizeof(float) * n_vis_rows * D)
             BSC_TRY(grow_dev((void **)&w->rows, &w->rows_cap, sizeof(float) * (n_vis_rows + n_vis_rows / 4 + 1024) * D));
-        hipLaunchKernelGGL(k_region_scatter, dim3(nblk), block, 0, s, n_cand, max_id, vcap, exact ? 1 : 0, cnt,
+        hipLaunchKernelGGL(k_region_scatter, dim3(nblk), block, 0, s, n_cand, v.max_id, v.vcap, v.exact, v.cnt,
                            (const uint8_t *)w->vis, (const int64_t *)w->blk_off, w->cidx, w->rowoff);
-        hipLaunchKernelGGL(k_region_gather_rows, dim3((unsigned)((n_vis * 64 + TPB - 1) / TPB)), block, 0, s, (int)n_vis, max_id, vcap,
-                           exact ? 1 : 0, x->c.cache_size, D, (const uint32_t *)w->cidx, (const int32_t *)w->rowoff, cnt,
-                           (const int32_t *)x->store_rows, rows, w->rows);
+        hipLaunchKernelGGL(k_region_gather_rows, dim3((unsigned)((n_vis * 64 + TPB - 1) / TPB)), block, 0, s, (int)n_vis, v.max_id, v.vcap,
+                           v.exact, v.cache_size, D, (const uint32_t *)w->cidx, (const int32_t *)w->rowoff, v.cnt, v.store_rows, rows,
+                           w->rows);
         scan_rows = w->rows; scan_n = n_vis_rows;
         rs = &w->rscale; rs_cap = &w->rscale_cap; rs_dirty = &scratch_dirty;
     }
@@ -1661,17 +1026,11 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
     int passes = 0;
     BSC_TRY(cosine_scan(x, scan_rows, scan_n, nq, rs, rs_cap, rs_dirty, &passes));
     stat_end(x, 1, (double)scan_n * D * 4.0 * passes + (double)nq * scan_n * 4.0);
-    if (all_open) {                        // no region anywhere: bsc_localize's own selection (its dense fast filter included)
-        CandArgs pa;
-        pa.n_cand = n_cand; pa.max_id = max_id; pa.vcap = vcap; pa.cache_size = x->c.cache_size; pa.exact = exact ? 1 : 0;
-        pa.use_radius = 0; pa.c0 = pa.c1 = pa.c2 = 0; pa.floor_lo = 0; pa.floor_hi = -1; pa.radius2 = 0.0;
-        pa.rgb_pos = x->rgb_pos; pa.cnt = cnt; pa.store_rows = x->store_rows; pa.name_rank = x->l_name_rank;
-        return select_and_copy_out(x, pa, nq, K, sstride, /*strict*/ 1, out_pos, out_sim, out_count);
-    }
+    if (all_open)                          // no region anywhere: bsc_localize's own selection (its dense fast filter included)
+        return select_and_copy_out(x, cand_args_open(v, n_cand), nq, K, sstride, /*strict*/ 1, out_pos, out_sim, out_count);
     RegionCandArgs ca;
+    (VoxelView &)ca = v;
     ca.n_cand = pruned ? (int)n_vis : n_cand;
-    ca.max_id = max_id; ca.vcap = vcap; ca.cache_size = x->c.cache_size; ca.exact = exact ? 1 : 0;
-    ca.rgb_pos = x->rgb_pos; ca.cnt = cnt; ca.store_rows = x->store_rows; ca.name_rank = x->l_name_rank;
     ca.regions = w->regions;
     ca.mask = pass ? w->mask : nullptr; ca.mask_stride = mask_stride;
     ca.cidx = pruned ? w->cidx : nullptr; ca.rowoff = pruned ? w->rowoff : nullptr;

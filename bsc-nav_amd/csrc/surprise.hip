@@ -111,12 +111,6 @@ __device__ __forceinline__ float dot4(const float4 a, const float4 b, float acc)
     return acc + ((a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w));
 }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // LDS + global written by lanes of this wavefront become visible to its other lanes
 __device__ __forceinline__ void wave_sync()
 {
