@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("BSC_LIB_PATH") or os.path.join(_HERE, "libbscnav.so")
 
 BSC_MODE_EXACT, BSC_MODE_MEAN, BSC_MODE_MAX = 0, 1, 2
 MODES = {"exact": BSC_MODE_EXACT, "mean": BSC_MODE_MEAN, "max": BSC_MODE_MAX}
+BSC_FLUSH_DISTANCE, BSC_FLUSH_SURPRISE = 0, 1         # bsc_set_flush_policy
+FLUSH_POLICIES = {"dist": BSC_FLUSH_DISTANCE, "surprise": BSC_FLUSH_SURPRISE}
 
 
 class BscConfig(C.Structure):
@@ -45,6 +47,10 @@ SIGNATURES = {
     "bsc_ingest_typed": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, DRAW_FN, _VP]),
     "bsc_flush": (_I32, [_VP, DRAW_FN, _VP]),
     "bsc_flush_surprise": (_I32, [_VP, _I32, _F64, _F64]),
+    "bsc_set_flush_policy": (_I32, [_VP, _I32, _I32, _F64, _F64]),
+    "bsc_store_usage": (_I32, [_VP, _VP]),
+    "bsc_compact_store": (_I32, [_VP, C.POINTER(_I64), C.POINTER(_I64)]),
+    "bsc_compact_stats": (_I32, [_VP, _VP]),
     "bsc_counters": (_I32, [_VP, _VP]),
     "bsc_geometry": (_I32, [_VP, _VP, _VP, _VP, _I64] + [_VP] * 8),
     "bsc_sort_pairs_u32": (_I32, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP]),

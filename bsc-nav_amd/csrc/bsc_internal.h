@@ -110,7 +110,14 @@ struct bsc_ctx {
     int32_t *store_rows; // (vcap+1,cache_size) pool rows; entry vcap is the grid_0_0_0 group
     int32_t *store_cnt;  // (vcap+1)
     int64_t n_flush;
-    int64_t pool_n_host;   // host mirror of DS_POOL_N (token pool rows in use), exact after every flush / import / reset
+    int64_t pool_n_host;   // host mirror of DS_POOL_N (token pool rows in use), exact after every flush / import / compaction / reset
+    // the flush bsc_ingest runs when a passing point meets a full cache (bsc_set_flush_policy; configuration: bsc_reset keeps it)
+    int32_t flush_policy, fp_radius;
+    double fp_sthr, fp_bthr;
+    // compaction scratch, kept and grown on demand (store_compact.hip): row marks, block totals / offsets, holes, movers, remap
+    void *cp_buf[6];
+    int64_t cp_cap[6];       // bytes
+    int64_t cp_runs, cp_rows_moved, cp_usec;   // compactions that moved rows, rows moved, host time spent in them (bsc_compact_stats)
     // dense modes
     float *acc;   // (vcap,D)
     int32_t *acnt; // (vcap)
@@ -260,6 +267,32 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+// sums of two per-thread ints over the workgroup's NT threads, exclusive per thread: (ea, eb), totals (ta, tb); one call per kernel
+template <int NT>
+__device__ __forceinline__ void block_scan2(int a, int b, int &ea, int &eb, int &ta, int &tb)
+{
+    __shared__ int s_a[NT / 64], s_b[NT / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int ia = a, ib = b;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int ua = __shfl_up(ia, o), ub = __shfl_up(ib, o);
+        if (lane >= o) { ia += ua; ib += ub; }
+    }
+    if (lane == 63) { s_a[wv] = ia; s_b[wv] = ib; }
+    __syncthreads();
+    int ba = 0, bb = 0;
+    ta = 0; tb = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+        const int va = s_a[w], vb = s_b[w];
+        ba += w < wv ? va : 0; bb += w < wv ? vb : 0;
+        ta += va; tb += vb;
+    }
+    ea = ba + ia - a;
+    eb = bb + ib - b;
+}
+
 // ---- primitives (prims.hip; rocPRIM device-wide sort and scans) ----
 size_t prim_workspace_bytes(size_t max_items);
 bsc_status prim_sort_keys(bsc_ctx *x, const u64 *in, u64 *out, size_t n, int begin_bit, int end_bit);
@@ -312,6 +345,16 @@ bsc_status ingest_batch(bsc_ctx *x, int32_t n_frames, const float *depth, const 
                         const double *alpha, bsc_draw_fn draw, void *user);
 bsc_status flush_cache(bsc_ctx *x, bsc_draw_fn draw, void *user);
 bsc_status grow_token_pool(bsc_ctx *x, int64_t need_rows);
+// room for n more pool rows before a flush changes anything: dead rows are reclaimed first (BSC_STORE_COMPACT=auto), the pool
+// grows only when the live rows + n still exceed it (store_compact.hip)
+bsc_status reserve_pool_rows(bsc_ctx *x, int64_t n);
+// the live rows (sum of store_cnt) to pool rows [0, live), DS_POOL_N = live; live_known < 0: counted here (store_compact.hip)
+bsc_status compact_store_impl(bsc_ctx *x, int64_t live_known, int64_t *rows_before, int64_t *rows_after);
+bool store_compact_auto();                  // BSC_STORE_COMPACT != never, read per call
+// store voxels / live tokens (sums over store_cnt or acnt) -> dscal[DS_TMP0 / DS_TMP1], enqueued on the main stream (capi.hip)
+bsc_status enqueue_store_totals(bsc_ctx *x);
+// the argument checks bsc_flush_surprise and bsc_set_flush_policy share (surprise.hip); `who` names the caller in the message
+bsc_status surprise_check_args(const bsc_ctx *x, const char *who, int32_t radius, double surprise_threshold, double boring_threshold);
 // update_memory_surp_base (surprise.hip): every iter_size row, tasks level by level; clears the cache like flush_cache
 bsc_status surprise_flush(bsc_ctx *x, int32_t radius, double surprise_threshold, double boring_threshold);
 bsc_status import_cache_impl(bsc_ctx *x, int64_t n_rows, const int32_t *pos_host, const float *feat_host, const float *dis_host);

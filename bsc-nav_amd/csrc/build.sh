@@ -14,7 +14,7 @@ if [ ! -f "$OBJ/host_rng.o" ] || [ "$HERE/host_rng.cpp" -nt "$OBJ/host_rng.o" ] 
   ( g++ -O3 -std=c++17 -fPIC -Wall -I"$HERE/../../include" -c "$HERE/host_rng.cpp" -o "$OBJ/host_rng.o" ) &
   pids+=($!)
 fi
-HIP_SOURCES="prims radix ingest dense flush surprise cosine_scan localize cluster frontier encoder_ops encoder_gemm capi"
+HIP_SOURCES="prims radix ingest dense flush store_compact surprise cosine_scan localize cluster frontier encoder_ops encoder_gemm capi"
 objs=("$OBJ/host_rng.o")
 for f in $HIP_SOURCES; do
   src="$HERE/$f.hip"; obj="$OBJ/$f.o"

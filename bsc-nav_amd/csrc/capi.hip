@@ -381,7 +381,7 @@ extern "C" void bsc_destroy(bsc_ctx *x)
                     x->d_transforms, x->d_offsets, x->f_rowdst, x->f_hit, x->f_hidx, x->f_rowseg, x->f_rowe,
                     x->f_headpos, x->f_win, x->f_draws, x->l_sims, x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b,
                     x->l_name_rank, x->l_q, x->l_qp, x->l_out_pos, x->l_out_sim, x->l_sel_key[0], x->l_sel_key[1], x->l_sel_val[0],
-                    x->l_sel_val[1], x->l_sel_thr, x->l_sel_cnt, x->l_valid, x->l_rscale, x->prim_tmp, x->prim_tmp_side, x->fr_mask, x->fr_in, x->fr_parent, x->fr_size,
+                    x->l_sel_val[1], x->l_sel_thr, x->l_sel_cnt, x->l_valid, x->l_rscale, x->cp_buf[0], x->cp_buf[1], x->cp_buf[2], x->cp_buf[3], x->cp_buf[4], x->cp_buf[5], x->prim_tmp, x->prim_tmp_side, x->fr_mask, x->fr_in, x->fr_parent, x->fr_size,
                     x->fr_ord, x->fr_roots, x->fr_labels, x->fr_first, x->fr_sizes, x->fr_scal, x->fr_sumx, x->fr_sumy,
                     x->fr_centers, x->fr_gains, x->log_cell, x->log_rec, x->stage_cell, x->stage_pos,
                     x->run_bits_s[0], x->run_bits_s[1], x->ck_run_s[0], x->ck_run_s[1], x->ck_start_s[0], x->ck_start_s[1], x->run_val_s[0], x->run_val_s[1]};
@@ -488,6 +488,55 @@ extern "C" bsc_status bsc_flush_surprise(bsc_ctx *x, int32_t neighbor_radius, do
     return surprise_flush(x, neighbor_radius, surprise_threshold, boring_threshold);
 }
 
+extern "C" bsc_status bsc_set_flush_policy(bsc_ctx *x, int32_t policy, int32_t neighbor_radius, double surprise_threshold,
+                                           double boring_threshold)
+{
+    if (!x) return BSC_E_INVALID;
+    if (x->c.mode != BSC_MODE_EXACT) { bsc_set_error("bsc_set_flush_policy: only the exact mode has a token cache"); return BSC_E_STATE; }
+    if (policy != BSC_FLUSH_DISTANCE && policy != BSC_FLUSH_SURPRISE) {
+        bsc_set_error("bsc_set_flush_policy: unknown policy %d", policy);
+        return BSC_E_INVALID;
+    }
+    if (policy == BSC_FLUSH_SURPRISE) {
+        BSC_TRY(surprise_check_args(x, "bsc_set_flush_policy", neighbor_radius, surprise_threshold, boring_threshold));
+        x->fp_radius = neighbor_radius;
+        x->fp_sthr = surprise_threshold;
+        x->fp_bthr = boring_threshold;
+    }
+    x->flush_policy = policy;
+    return BSC_OK;
+}
+
+extern "C" bsc_status bsc_store_usage(bsc_ctx *x, int64_t *out3)
+{
+    if (!x || !out3) return BSC_E_INVALID;
+    if (x->c.mode != BSC_MODE_EXACT) { bsc_set_error("bsc_store_usage: only the exact mode has a token pool"); return BSC_E_STATE; }
+    BSC_HIP(hipSetDevice(x->device));
+    BSC_TRY(enqueue_store_totals(x));
+    BSC_TRY(read_scalars(x));
+    out3[0] = x->hscal[DS_POOL_N];
+    out3[1] = x->hscal[DS_TMP1];
+    out3[2] = x->c.token_capacity;
+    return BSC_OK;
+}
+
+extern "C" bsc_status bsc_compact_store(bsc_ctx *x, int64_t *rows_before, int64_t *rows_after)
+{
+    if (!x) return BSC_E_INVALID;
+    if (x->c.mode != BSC_MODE_EXACT) { bsc_set_error("bsc_compact_store: only the exact mode has a token pool"); return BSC_E_STATE; }
+    BSC_HIP(hipSetDevice(x->device));
+    return compact_store_impl(x, -1, rows_before, rows_after);
+}
+
+extern "C" bsc_status bsc_compact_stats(bsc_ctx *x, int64_t *out3)
+{
+    if (!x || !out3) return BSC_E_INVALID;
+    out3[0] = x->cp_runs;
+    out3[1] = x->cp_rows_moved;
+    out3[2] = x->cp_usec;
+    return BSC_OK;
+}
+
 __global__ __launch_bounds__(TPB) void k_store_totals(int n, const int32_t *__restrict__ cnt, int64_t *out2)
 {
     __shared__ long long sv[TPB], st[TPB];
@@ -509,13 +558,20 @@ __global__ __launch_bounds__(TPB) void k_store_totals(int n, const int32_t *__re
     }
 }
 
+bsc_status enqueue_store_totals(bsc_ctx *x)
+{
+    const int32_t *cnt = x->c.mode == BSC_MODE_EXACT ? x->store_cnt : x->acnt;
+    const int n = x->c.voxel_capacity + 1;
+    BSC_HIP(hipMemsetAsync(x->dscal + DS_TMP0, 0, sizeof(int64_t) * 2, x->stream));
+    hipLaunchKernelGGL(k_store_totals, dim3(512), dim3(TPB), 0, x->stream, n, cnt, x->dscal + DS_TMP0);
+    return BSC_OK;
+}
+
 extern "C" bsc_status bsc_counters(bsc_ctx *x, int64_t *out)
 {
     if (!x || !out) return BSC_E_INVALID;
     BSC_HIP(hipSetDevice(x->device));
-    const int32_t *cnt = x->c.mode == BSC_MODE_EXACT ? x->store_cnt : x->acnt;
-    BSC_HIP(hipMemsetAsync(x->dscal + DS_TMP0, 0, sizeof(int64_t) * 2, x->stream));
-    hipLaunchKernelGGL(k_store_totals, dim3(512), dim3(TPB), 0, x->stream, x->c.voxel_capacity + 1, cnt, x->dscal + DS_TMP0);
+    BSC_TRY(enqueue_store_totals(x));
     BSC_TRY(read_scalars(x));
     out[0] = x->hscal[DS_MAX_ID];
     out[1] = x->iter_id;

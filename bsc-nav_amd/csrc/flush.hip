@@ -167,9 +167,9 @@ bsc_status flush_cache(bsc_ctx *x, bsc_draw_fn draw, void *user)
     const dim3 block(TPB), grid((n + TPB - 1) / TPB), wgrid((unsigned)(((int64_t)n * 64 + TPB - 1) / TPB));
     const int ebits = ceil_log2_u64((uint64_t)x->c.voxel_capacity + 2);
     // A flush appends at most one pool row per cache row.  The reference's HDF5 store is unbounded (memory_2.py:330-354), so
-    // the pool GROWS here when this flush could overflow it — before anything is changed: a flush triggered from the middle
-    // of an ingest call (memory_2.py:880-881) must never fail half way through the frame.
-    BSC_TRY(grow_token_pool(x, x->pool_n_host + n));
+    // the pool GROWS here (after dead rows were reclaimed) when this flush could overflow it — before anything is changed: a
+    // flush triggered from the middle of an ingest call (memory_2.py:880-881) must never fail half way through the frame.
+    BSC_TRY(reserve_pool_rows(x, n));
     hipLaunchKernelGGL(k_flush_keys, grid, block, 0, s, n, x->cache_pos, x->occ, x->c.grid_size, x->nh,
                        x->c.voxel_capacity, x->f_keys_a);
     BSC_TRY(prim_sort_keys(x, x->f_keys_a, x->f_keys_b, (size_t)n, 0, 20 + ebits));

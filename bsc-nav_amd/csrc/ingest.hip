@@ -2093,7 +2093,7 @@ bsc_status ingest_batch(bsc_ctx *x, int32_t n_frames, const float *depth, const 
     if (chain_eager) BSC_TRY(launch_pending_chain(x));      // A/B: the chain right behind its order stage instead of at the next call
     if (x->c.mode == BSC_MODE_EXACT) {
         // memory_2.py:880-886: rows fill the cache in order; the point that finds it full triggers the
-        // flush and loses its own token.
+        // flush (:881, the policy of bsc_set_flush_policy) and loses its own token.
         int64_t remaining = x->hscal[DS_B_NPASS], q = 0;
         while (remaining > 0) {
             const int64_t room = x->c.iter_size - x->iter_id;
@@ -2112,7 +2112,8 @@ bsc_status ingest_batch(bsc_ctx *x, int32_t n_frames, const float *depth, const 
                 x->iter_id += n; q += n; remaining -= n;
             }
             if (remaining > 0) {        // next passing point meets a full cache
-                BSC_TRY(flush_cache(x, draw, user));
+                if (x->flush_policy == BSC_FLUSH_SURPRISE) BSC_TRY(surprise_flush(x, x->fp_radius, x->fp_sthr, x->fp_bthr));
+                else BSC_TRY(flush_cache(x, draw, user));
                 q += 1; remaining -= 1;
             }
         }

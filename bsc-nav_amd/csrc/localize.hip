@@ -831,31 +831,6 @@ static bsc_status region_ws_get(bsc_ctx *x, RegionWs **out)
     return BSC_OK;
 }
 
-// sums of two per-thread ints over the workgroup's TPB threads, exclusive per thread: (ea, eb), totals (ta, tb)
-__device__ __forceinline__ void block_scan2(int a, int b, int &ea, int &eb, int &ta, int &tb)
-{
-    __shared__ int s_a[TPB / 64], s_b[TPB / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int ia = a, ib = b;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int ua = __shfl_up(ia, o), ub = __shfl_up(ib, o);
-        if (lane >= o) { ia += ua; ib += ub; }
-    }
-    if (lane == 63) { s_a[wv] = ia; s_b[wv] = ib; }
-    __syncthreads();
-    int ba = 0, bb = 0;
-    ta = 0; tb = 0;
-#pragma unroll
-    for (int w = 0; w < TPB / 64; ++w) {
-        const int va = s_a[w], vb = s_b[w];
-        ba += w < wv ? va : 0; bb += w < wv ? vb : 0;
-        ta += va; tb += vb;
-    }
-    ea = ba + ia - a;
-    eb = bb + ib - b;
-}
-
 __global__ __launch_bounds__(TPB) void k_region_visibility(int n_cand, int max_id, int vcap, int exact,
                                                            const int32_t *__restrict__ rgb_pos, const int32_t *__restrict__ cnt,
                                                            const RegionDev *__restrict__ regions, int nq,
@@ -884,7 +859,7 @@ __global__ __launch_bounds__(TPB) void k_region_visibility(int n_cand, int max_i
     const int seen = any != 0u ? 1 : 0;
     if (in) vis[c] = (uint8_t)seen;
     int ea, eb, ta, tb;
-    block_scan2(seen, seen ? (exact ? m : 1) : 0, ea, eb, ta, tb);
+    block_scan2<TPB>(seen, seen ? (exact ? m : 1) : 0, ea, eb, ta, tb);
     if (threadIdx.x == 0) blk_tot[blockIdx.x] = ((int64_t)ta << RG_ROWS_BITS) | (int64_t)tb;
 }
 
@@ -896,7 +871,7 @@ __global__ __launch_bounds__(TPB) void k_region_scatter(int n_cand, int max_id, 
     const int seen = (c < n_cand && vis[c]) ? 1 : 0;
     const int nr = seen ? (exact ? cnt[(c == max_id) ? vcap : c] : 1) : 0;
     int ea, eb, ta, tb;
-    block_scan2(seen, nr, ea, eb, ta, tb);
+    block_scan2<TPB>(seen, nr, ea, eb, ta, tb);
     if (!seen) return;
     const int64_t base = blk_off[blockIdx.x];
     const int64_t i = (base >> RG_ROWS_BITS) + ea;

@@ -639,29 +639,44 @@ __global__ __launch_bounds__(TPB) void k_surp_task(SurpArgs a)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
+// k_surp_task's dynamic LDS: pool rows and inverse norms of the neighbour tokens, one token
+static size_t surp_task_lds(int radius, int cs, int D)
+{
+    const int w = 2 * radius + 1;
+    return sizeof(float) * (2 * (size_t)(w * w * w - 1) * cs + D);
+}
+
+bsc_status surprise_check_args(const bsc_ctx *x, const char *who, int32_t radius, double sthr, double bthr)
+{
+    if (radius < 0 || radius > SURP_RMAX) {
+        bsc_set_error("%s: neighbor_radius %d outside [0, %d]", who, radius, SURP_RMAX);
+        return BSC_E_INVALID;
+    }
+    if (sthr != sthr || bthr != bthr) {
+        bsc_set_error("%s: NaN threshold", who);
+        return BSC_E_INVALID;
+    }
+    const int cs = x->c.cache_size;
+    const size_t lds = surp_task_lds(radius, cs, x->c.token_dim);
+    if (cs > 64 || lds > SURP_TASK_LDS) {
+        bsc_set_error("%s: cache_size %d with radius %d needs %zu bytes of LDS (limit %d; cache_size <= 64)", who, cs, radius, lds,
+                      SURP_TASK_LDS);
+        return BSC_E_INVALID;
+    }
+    return BSC_OK;
+}
+
 bsc_status surprise_flush(bsc_ctx *x, int32_t radius, double sthr, double bthr)
 {
     const int n = x->c.iter_size, D = x->c.token_dim, cs = x->c.cache_size, vcap = x->c.voxel_capacity;
     const int w = 2 * radius + 1, K = w * w * w;
     hipStream_t s = x->stream;
-    if (radius < 0 || radius > SURP_RMAX) {
-        bsc_set_error("bsc_flush_surprise: neighbor_radius %d outside [0, %d]", radius, SURP_RMAX);
-        return BSC_E_INVALID;
-    }
-    if (sthr != sthr || bthr != bthr) {
-        bsc_set_error("bsc_flush_surprise: NaN threshold");
-        return BSC_E_INVALID;
-    }
-    const size_t lds = sizeof(float) * (2 * (size_t)(K - 1) * cs + D);
-    if (cs > 64 || lds > SURP_TASK_LDS) {
-        bsc_set_error("bsc_flush_surprise: cache_size %d with radius %d needs %zu bytes of LDS (limit %d; cache_size <= 64)", cs,
-                      radius, lds, SURP_TASK_LDS);
-        return BSC_E_INVALID;
-    }
+    BSC_TRY(surprise_check_args(x, "bsc_flush_surprise", radius, sthr, bthr));
+    const size_t lds = surp_task_lds(radius, cs, D);
     BSC_TRY(ws_ensure(x, K));
     SurpriseWs *ws = x->surp;
-    // at most one new pool row per cache row, grown before anything changes (as flush_cache)
-    BSC_TRY(grow_token_pool(x, x->pool_n_host + n));
+    // at most one new pool row per cache row: dead rows reclaimed / the pool grown before anything changes (as flush_cache)
+    BSC_TRY(reserve_pool_rows(x, n));
     const dim3 block(TPB), grid((n + TPB - 1) / TPB), wgrid((unsigned)(((int64_t)n * 64 + TPB - 1) / TPB));
     hipLaunchKernelGGL(k_surp_rows, grid, block, 0, s, n, x->cache_pos, x->occ, x->c.grid_size, x->nh, vcap, ws->ent, ws->head);
     hipLaunchKernelGGL(k_surp_rowinv, wgrid, block, 0, s, n, x->cache_f, D, ws->inv);
@@ -720,6 +735,8 @@ bsc_status surprise_flush(bsc_ctx *x, int32_t radius, double sthr, double bthr)
     free(cnt);
     free(off);
     BSC_HIP(hipGetLastError());
+    // the live rows (sum of the groups' counts) ride in the readback below: merges leave pool rows behind that nothing refers to
+    BSC_TRY(enqueue_store_totals(x));
     BSC_TRY(read_scalars(x));
     if (x->hscal[DS_ERROR]) {
         bsc_set_error("capacity exceeded during the surprise flush (code %lld; token_capacity=%lld)", (long long)x->hscal[DS_ERROR],
@@ -735,6 +752,11 @@ bsc_status surprise_flush(bsc_ctx *x, int32_t radius, double sthr, double bthr)
     x->n_flush++;
     x->names_dirty = true; x->row_scale_dirty = true;
     x->pool_n_host = x->hscal[DS_POOL_N];
+    // more dead rows than live ones: move the live rows down (at most `live` moves after at least `live` allocations)
+    const int64_t live = x->hscal[DS_TMP1];
+    // The flush is complete at this point and the compaction is optional: when it cannot run (its scratch could not be
+    // allocated) the pool stays as it is — nothing was moved — and the flush still succeeds; the error text names the cause.
+    if (x->pool_n_host > 2 * live && store_compact_auto()) (void)compact_store_impl(x, live, nullptr, nullptr);
     return BSC_OK;
 }
 

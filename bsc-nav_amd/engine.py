@@ -139,6 +139,8 @@ class VoxelEngine:
         self.log_capacity = 0
         self._last_localize = None      # (Q, K, counts) of the last localize call: its results stay on the GPU for clustering
         self._draw = _lib.DRAW_FN(self._draw_cb)
+        self._no_draw = _lib.DRAW_FN()    # NULL: what ingest hands over under the surprise policy, which never draws
+        self._flush_policy = "dist"
 
     # memory_2.py:352 — Python's global RNG, one draw per row that meets a full voxel
     def _draw_cb(self, user, n, out):
@@ -211,7 +213,8 @@ class VoxelEngine:
         self._enter(depth, rgb, tokens, sample_idx, alpha)
         _lib.check(self.lib.bsc_ingest_typed(self.h, F, _dp(depth), _dp(rgb), rgb.shape[-1], _dp(tokens),
                                              1 if tokens.dtype == torch.bfloat16 else 0, _hp(T), _dp(sample_idx),
-                                             _hp(off), _dp(alpha), self._draw, None))
+                                             _hp(off), _dp(alpha),
+                                             self._draw if self._flush_policy == "dist" else self._no_draw, None))
 
     def flush(self):
         _lib.check(self.lib.bsc_flush(self.h, self._draw, None))
@@ -219,6 +222,36 @@ class VoxelEngine:
     def flush_surprise(self, radius=1, surprise_threshold=0.5, boring_threshold=0.95):
         """update_memory_surp_base (memory_2.py:364-536) over every cache row; exact mode only."""
         _lib.check(self.lib.bsc_flush_surprise(self.h, int(radius), float(surprise_threshold), float(boring_threshold)))
+
+    def set_flush_policy(self, policy="dist", radius=1, surprise_threshold=0.5, boring_threshold=0.95):
+        """The flush ingest() runs when a passing point meets a full cache (memory_2.py:880-881): "dist"
+        (update_memory_dist_base, the default) or "surprise" (update_memory_surp_base with these three parameters, no draws).
+        Exact mode only; kept across reset(); a refused call leaves the previous policy in place."""
+        if policy not in _lib.FLUSH_POLICIES:
+            raise ValueError(f"flush policy {policy!r}: expected one of {sorted(_lib.FLUSH_POLICIES)}")
+        _lib.check(self.lib.bsc_set_flush_policy(self.h, _lib.FLUSH_POLICIES[policy], int(radius), float(surprise_threshold),
+                                                 float(boring_threshold)))
+        self._flush_policy = policy
+
+    def store_usage(self):
+        """dict(pool_rows, live_rows, capacity): token-pool rows in use, rows some voxel's group still refers to, rows
+        allocated (exact mode).  pool_rows > live_rows after merges of the surprise policy, until the store is compacted."""
+        out = np.zeros(3, np.int64)
+        _lib.check(self.lib.bsc_store_usage(self.h, _hp(out)))
+        return dict(pool_rows=int(out[0]), live_rows=int(out[1]), capacity=int(out[2]))
+
+    def compact_store(self):
+        """Move the live token rows to the front of the pool (bsc_compact_store) -> (pool rows before, after)."""
+        before, after = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.bsc_compact_store(self.h, C.byref(before), C.byref(after)))
+        return before.value, after.value
+
+    def compact_stats(self):
+        """dict(compactions, rows_moved, ms): compactions since the engine was created that moved rows — explicit and automatic
+        ones —, the rows they moved and the host time they took."""
+        out = np.zeros(3, np.int64)
+        _lib.check(self.lib.bsc_compact_stats(self.h, _hp(out)))
+        return dict(compactions=int(out[0]), rows_moved=int(out[1]), ms=out[2] / 1e3)
 
     def counters(self):
         out = np.zeros(10, np.int64)

@@ -78,6 +78,9 @@ class VoxelTokenMemory:
         self.neighbor_radius = 1                                               # memory_2.py:113-115 (update_memory_surp_base)
         self.boring_threshold = 0.95
         self.surprise_threshold = 0.5
+        # which update the full cache gets inside obs2voxeltoken (memory_2.py:880-881): "dist" (update_memory_dist_base, the
+        # reference's line as shipped) or "surprise" (update_memory_surp_base with the three attributes above, read per call)
+        self.flush_policy = getattr(args, "flush_policy", "dist")
         self.camera_height = c.sensor_height
         self.floor_height, self.map_height = c.floor_height, c.map_height
         self.maxh = int(self.map_height / self.cs)                             # memory_2.py:122-123
@@ -102,8 +105,20 @@ class VoxelTokenMemory:
                                   token_capacity=self._token_capacity, max_points=self._max_frames * c.height * c.width,
                                   device=self.gpu, min_depth=self.min_depth, max_depth=self.max_depth,
                                   min_h=self.minh, max_h=self.maxh)
+        self._pushed_policy = ("dist",)                          # a new context flushes by distance
         self.chain.reset()
         self._touch()
+
+    def _push_flush_policy(self):
+        """The automatic flush of the coming ingest follows flush_policy / neighbor_radius / surprise_threshold /
+        boring_threshold as they are now (exact mode; the engine is told only when the tuple changed)."""
+        if self.feature_mode != "exact":
+            return
+        want = ("dist",) if self.flush_policy == "dist" else (
+            self.flush_policy, int(self.neighbor_radius), float(self.surprise_threshold), float(self.boring_threshold))
+        if want != getattr(self, "_pushed_policy", ("dist",)):
+            self.engine.set_flush_policy(*want)
+            self._pushed_policy = want
 
     def _log(self, *a):
         if not self.quiet:
@@ -266,6 +281,7 @@ class VoxelTokenMemory:
         if self.alpha_source == "host":
             with np.errstate(all="ignore"):
                 alpha = torch.from_numpy(self._host_alpha(depth, idx)).to(self.device)
+        self._push_flush_policy()
         self.engine.ingest(torch.from_numpy(depth).to(self.device).unsqueeze(0), d_rgb, patch_tokens, T[None],
                            torch.from_numpy(idx).to(self.device), np.array([0, len(idx)], np.int64), alpha)
         self._touch()
@@ -306,6 +322,7 @@ class VoxelTokenMemory:
         if tokens is None:
             tokens = self._batch_patch_tokens(rgb)
         self._touch()
+        self._push_flush_policy()
         host_alpha = self.alpha_source == "host"
         if self.depth_sample_rate == 1 and self.feature_mode != "exact" and not host_alpha:
             self.engine.ingest(depth, rgb, tokens, Ts)

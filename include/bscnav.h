@@ -80,7 +80,7 @@ bsc_status bsc_reset(bsc_ctx *ctx);
  *               exp(-r2/1.2) (memory_2.py:873-875); NULL = computed on the device
  * Frame order and point order inside the call define the sequential semantics (first-touch ids,
  * rgb running mean, top-down map ties, token-cache order).  In exact mode draw() is called when a
- * token-cache flush meets full voxels. */
+ * token-cache flush under the distance policy meets full voxels (bsc_set_flush_policy selects the flush). */
 bsc_status bsc_ingest(bsc_ctx *ctx, int32_t n_frames, const float *depth_dev, const uint8_t *rgb_dev,
                       int32_t rgb_channels, const float *tokens_dev, const double *transforms_host,
                       const int32_t *sample_idx_dev, const int64_t *offsets_host, const double *alpha_dev,
@@ -110,6 +110,39 @@ bsc_status bsc_flush(bsc_ctx *ctx, bsc_draw_fn draw, void *user);
  * are legal and compare as in Python: surprise_threshold = +inf only creates groups (+inf > +inf is false, also for a row
  * without neighbour tokens), -inf accepts every row whose surprise is not NaN; boring_threshold = +inf never merges. */
 bsc_status bsc_flush_surprise(bsc_ctx *ctx, int32_t neighbor_radius, double surprise_threshold, double boring_threshold);
+
+/* The flush bsc_ingest / bsc_ingest_typed run when a passing point meets a full token cache (memory_2.py:880-881: the line a
+ * user of the reference edits to choose between update_memory_dist_base and update_memory_surp_base).  The order of events does
+ * not change: rows fill the cache in order, the point that finds it full triggers the flush and loses its own token (:880-886),
+ * the next row is cache row 0, the flush counter advances.  Under BSC_FLUSH_SURPRISE that flush is exactly one
+ * bsc_flush_surprise(ctx, neighbor_radius, surprise_threshold, boring_threshold) over the full cache (no zero tail there); draw
+ * is never called and may be NULL.  bsc_flush and bsc_flush_surprise called explicitly do what they always do.  The three
+ * parameters are ignored for BSC_FLUSH_DISTANCE.  The policy is configuration: bsc_reset keeps it.
+ * BSC_E_STATE in the dense modes; BSC_E_INVALID for an unknown policy and for everything bsc_flush_surprise refuses (radius
+ * outside [0, 3], a NaN threshold, cache_size > 64, the LDS bound) — the previous policy then stays in place.  Infinite
+ * thresholds are legal, with the meanings given at bsc_flush_surprise. */
+#define BSC_FLUSH_DISTANCE 0   /* update_memory_dist_base, memory_2.py:326-358 (default) */
+#define BSC_FLUSH_SURPRISE 1   /* update_memory_surp_base, memory_2.py:364-536           */
+bsc_status bsc_set_flush_policy(bsc_ctx *ctx, int32_t policy, int32_t neighbor_radius, double surprise_threshold,
+                                double boring_threshold);
+
+/* The token pool behind the store (exact mode only, BSC_E_STATE otherwise).  A merge of update_memory_surp_base
+ * (memory_2.py:427-436) keeps the mean in the pool row of the component's smallest slot; the rows of the other merged tokens
+ * stay allocated and nothing refers to them, so the rows in use grow by up to iter_size per surprise flush while the live store
+ * is bounded by voxels x cache_size — and the exact-mode scan of bsc_localize streams every row in use.
+ *   bsc_store_usage    out[0] = pool rows in use, out[1] = live rows (sum of the groups' counts, grid_0_0_0 included),
+ *                      out[2] = pool capacity in rows
+ *   bsc_compact_store  moves the live rows so that they occupy pool rows [0, live), in place, each moved row copied once;
+ *                      rows in use = live afterwards (*rows_before_host / *rows_after_host, either may be NULL).  Nothing a
+ *                      caller can observe changes: exports, localize results and later flushes are the same.
+ * The library compacts on its own before it would grow the pool (any flush) and after a surprise flush that leaves more dead
+ * rows than live ones; BSC_STORE_COMPACT=never (environment, read per call; default auto) switches those two off, not
+ * bsc_compact_store.  A compaction the library runs after a flush is optional: when it cannot run, the flush still succeeds.
+ *   bsc_compact_stats  since bsc_create, explicit and automatic together: out[0] = compactions that moved rows, out[1] = rows
+ *                      moved, out[2] = host time spent in them in microseconds (each ends with a stream synchronize) */
+bsc_status bsc_store_usage(bsc_ctx *ctx, int64_t *out3_host);
+bsc_status bsc_compact_store(bsc_ctx *ctx, int64_t *rows_before_host, int64_t *rows_after_host);
+bsc_status bsc_compact_stats(bsc_ctx *ctx, int64_t *out3_host);
 
 /* counters (host sync): out[0]=max_id out[1]=iter_id out[2]=store voxels out[3]=store tokens
  * out[4]=flushes out[5]=points passed so far out[6]=points seen so far out[7]=voxel-row RMWs (dense)
