@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/bscnav.h"
+#include "ctx_mem.h"
 
 typedef unsigned long long u64;
 // per-point payload of the rgb chain: one 12-byte gather per point
@@ -66,6 +67,7 @@ struct RegionWs;     // localize.hip: scratch of bsc_localize_regions, allocated
 struct ClusterWs;    // cluster.hip: inputs, result block and pinned staging of bsc_cluster_centers(_batch), grown on demand
 
 struct bsc_ctx {
+    BscMem *mem;               // owns every device / pinned-host buffer below (ctx_mem.h): created first, released last
     bsc_config c;
     int device;
     hipStream_t stream;
@@ -213,6 +215,7 @@ struct bsc_ctx {
     int32_t last_counts[1024];
     ClusterWs *clus;                // bsc_cluster_centers / bsc_cluster_centers_batch workspace (nullptr until the first call)
     // frontier helpers (allocated on first use, gs*gs each)
+    bool fr_ready;             // all of them exist (frontier.hip fr_alloc)
     uint8_t *fr_mask, *fr_in;
     int32_t *fr_parent, *fr_size, *fr_ord, *fr_roots, *fr_labels, *fr_first, *fr_sizes, *fr_scal;
     unsigned long long *fr_sumx, *fr_sumy;
@@ -231,6 +234,7 @@ struct bsc_ctx {
     hipStream_t copy;             // early readback of those counts while the main stream goes on with the pair tiles
     void *h2d_pin[4];             // pinned staging of the pageable-host imports (capi.hip h2d_pipelined), allocated on first use
     hipEvent_t h2d_ev[4];
+    bool h2d_ready;               // all four buffers and events exist
     bool ev_runs_valid;
     int last_order_set;        // scratch set of the last order stage enqueued on the side stream (-1: none): its ev_ready marks it complete
     // bookkeeping
@@ -242,7 +246,6 @@ struct bsc_ctx {
     bool timing;
 };
 
-void bsc_set_error(const char *fmt, ...);
 #define BSC_HIP(expr)                                                                          \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
@@ -256,8 +259,6 @@ void bsc_set_error(const char *fmt, ...);
         bsc_status _s = (expr);       \
         if (_s != BSC_OK) return _s;  \
     } while (0)
-// a function shared between translation units that stays out of the library's dynamic symbol table
-#define BSC_LOCAL __attribute__((visibility("hidden")))
 
 // sum of v over the wavefront's 64 lanes, in every lane (xor butterfly, distances 32 .. 1)
 __device__ __forceinline__ float wave_sum(float v)
@@ -305,8 +306,7 @@ bsc_status prim_sort_pairs_u32(bsc_ctx *x, const uint32_t *kin, uint32_t *kout, 
 bsc_status prim_sort_pairs_u32_onesweep(bsc_ctx *x, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
                                         size_t n, int begin_bit, int end_bit);
 // in-tree onesweep radix sort of (u32 key, u32 value) pairs on the key bits [b0, b1): stable, input preserved (radix.hip)
-bsc_status radix_ws_create(RadixWs *ws, size_t max_items);
-void radix_ws_destroy(RadixWs *ws);
+bsc_status radix_ws_create(BscMem *m, RadixWs *ws, size_t max_items);      // the buffers are the ledger's
 bsc_status radix_sort_pairs_u32(bsc_ctx *x, RadixWs *ws, hipStream_t st, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
                                 uint32_t *vout, size_t n, int b0, int b1);
 bsc_status prim_exclusive_sum_i64(bsc_ctx *x, const int64_t *in, int64_t *out, size_t n);
@@ -358,7 +358,6 @@ bsc_status surprise_check_args(const bsc_ctx *x, const char *who, int32_t radius
 // update_memory_surp_base (surprise.hip): every iter_size row, tasks level by level; clears the cache like flush_cache
 bsc_status surprise_flush(bsc_ctx *x, int32_t radius, double surprise_threshold, double boring_threshold);
 bsc_status import_cache_impl(bsc_ctx *x, int64_t n_rows, const int32_t *pos_host, const float *feat_host, const float *dis_host);
-void surprise_ws_free(bsc_ctx *x);   // exact mode: the token store is unbounded like the reference's
 bsc_status launch_pending_chain(bsc_ctx *x);
 bsc_status launch_keys_pairs(bsc_ctx *x, int64_t P, int n_frames, bool all_pixels, const uint32_t *p_patf);
 bsc_status frontier_mask_impl(bsc_ctx *x, const uint8_t *navigable_host, uint8_t *mask_host);
@@ -374,8 +373,6 @@ bsc_status localize_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, 
                          int32_t floor_lo, int32_t floor_hi, int32_t *out_pos, float *out_sim, int32_t *out_count);
 bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, const bsc_region *regions,
                                  int32_t *out_pos, float *out_sim, int32_t *out_count);
-void region_ws_free(bsc_ctx *x);
-void cluster_ws_free(bsc_ctx *x);    // cluster.hip
 // ---- the cosine scan (cosine_scan.hip), as localize.hip calls it ----
 int64_t sims_row_stride(int64_t n_rows);   // floats between the similarity rows of consecutive queries
 // q_dev (nq, D) -> x->l_q: normalised, zero-padded to the whole query tiles the matrix-core kernels read
@@ -388,8 +385,6 @@ BSC_LOCAL bsc_status refresh_row_scales(bsc_ctx *x, const float *rows, int64_t n
 // apart.  *passes_out = times the matrix was streamed.
 BSC_LOCAL bsc_status cosine_scan(bsc_ctx *x, const float *rows, int64_t n_rows, int nq, float2 **rs, int64_t *rs_cap, bool *rs_dirty,
                                  int *passes_out);
-// localize scratch: *p holds at least need_bytes afterwards (contents are not kept; no slack: callers add their own)
-BSC_LOCAL bsc_status grow_dev(void **p, int64_t *cap, int64_t need_bytes);
 bsc_status pool_query_impl(bsc_ctx *x, const float *tokens, int32_t B, int32_t T, int32_t D, float *out);
 bsc_status read_scalars(bsc_ctx *x); // dscal -> hscal (synchronises the main stream)
 void localize_prepare(bsc_ctx *x);   // name ranks + row scales of the batched scan, eagerly (localize.hip; the imports call it)

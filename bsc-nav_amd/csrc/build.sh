@@ -8,19 +8,20 @@ OUT="${BSC_OUT:-$HERE/../libbscnav.so}"
 OBJ="${BSC_OBJ:-$HERE/_obj}"
 mkdir -p "$OBJ"
 FLAGS="${BSC_EXTRA_FLAGS} --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result"
+ROCM="${ROCM_PATH:-$(dirname "$(dirname "$(readlink -f "$(command -v hipcc)")")")}"
+# *.cpp: host-only C++ for plain g++ — host_rng (NumPy's MT19937 shuffle restated, AVX2 paths behind a runtime check), ctx_mem
+# (the ledger of a context's device / pinned-host memory: the declarations of the HIP runtime API, no device code)
+SOURCES="host_rng.cpp ctx_mem.cpp prims.hip radix.hip ingest.hip dense.hip flush.hip store_compact.hip surprise.hip cosine_scan.hip localize.hip cluster.hip frontier.hip encoder_ops.hip encoder_gemm.hip capi.hip"
 pids=()
-# host_rng.cpp: host-only C++ (NumPy's MT19937 shuffle restated, AVX2 paths behind a runtime check) — plain g++
-if [ ! -f "$OBJ/host_rng.o" ] || [ "$HERE/host_rng.cpp" -nt "$OBJ/host_rng.o" ] || [ "$HERE/../../include/bscnav.h" -nt "$OBJ/host_rng.o" ]; then
-  ( g++ -O3 -std=c++17 -fPIC -Wall -I"$HERE/../../include" -c "$HERE/host_rng.cpp" -o "$OBJ/host_rng.o" ) &
-  pids+=($!)
-fi
-HIP_SOURCES="prims radix ingest dense flush store_compact surprise cosine_scan localize cluster frontier encoder_ops encoder_gemm capi"
-objs=("$OBJ/host_rng.o")
-for f in $HIP_SOURCES; do
-  src="$HERE/$f.hip"; obj="$OBJ/$f.o"
+objs=()
+for f in $SOURCES; do
+  src="$HERE/$f"; obj="$OBJ/${f%.*}.o"
   objs+=("$obj")
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/bsc_internal.h" -nt "$obj" ] || [ "$HERE/geometry_dev.h" -nt "$obj" ] || [ "$HERE/../../include/bscnav.h" -nt "$obj" ]; then
-    ( hipcc $FLAGS -c "$src" -o "$obj" ) &
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/bsc_internal.h" -nt "$obj" ] || [ "$HERE/ctx_mem.h" -nt "$obj" ] || [ "$HERE/geometry_dev.h" -nt "$obj" ] || [ "$HERE/../../include/bscnav.h" -nt "$obj" ]; then
+    case "$f" in
+      *.cpp) ( g++ -O3 -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I"$ROCM/include" -I"$HERE/../../include" -c "$src" -o "$obj" ) & ;;
+      *) ( hipcc $FLAGS -c "$src" -o "$obj" ) & ;;
+    esac
     pids+=($!)
   fi
 done

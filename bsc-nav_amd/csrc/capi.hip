@@ -59,16 +59,7 @@ static void fill(bsc_ctx *x, T *p, int64_t n, T v)
     hipLaunchKernelGGL((k_fill<T>), dim3((unsigned)blocks), dim3(TPB), 0, x->stream, p, n, v);
 }
 
-#define ALLOC(ptr, count)                                                               \
-    do {                                                                                \
-        size_t _b = sizeof(*(ptr)) * (size_t)(count);                                   \
-        hipError_t _e = hipMalloc((void **)&(ptr), _b ? _b : 16);                       \
-        if (_e != hipSuccess) {                                                         \
-            bsc_set_error("hipMalloc(%zu bytes) for %s: %s", _b, #ptr, hipGetErrorString(_e)); \
-            bsc_destroy(x);                                                             \
-            return BSC_E_HIP;                                                           \
-        }                                                                               \
-    } while (0)
+#define ALLOC(ptr, count) BSC_TRY(mem_alloc(x->mem, (void **)&(ptr), sizeof(*(ptr)) * (size_t)(count), #ptr))
 
 static bsc_status reset_state(bsc_ctx *x)
 {
@@ -143,36 +134,11 @@ static bool proj_identity(int n, double kinv_a, double kinv_b, double k_a, doubl
     return true;
 }
 
-extern "C" bsc_status bsc_create(const bsc_config *cfg, int32_t device, void *hip_stream, bsc_ctx **out)
+// every buffer, stream and event of a new context; on any failure the caller (bsc_create) destroys what exists
+static bsc_status ctx_build(bsc_ctx *x)
 {
-    if (!cfg || !out) { bsc_set_error("bsc_create: null argument"); return BSC_E_INVALID; }
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        bsc_set_error("bsc_create: no HIP device visible (libbscnav has no CPU path)");
-        return BSC_E_HIP;
-    }
-    if (device < 0 || device >= ndev) { bsc_set_error("bsc_create: device %d of %d", device, ndev); return BSC_E_INVALID; }
-    const bsc_config &c = *cfg;
-    const int64_t nh = (int64_t)c.max_h - c.min_h;
-    const int64_t ncell = (int64_t)c.grid_size * c.grid_size * nh;
-    if (c.height <= 0 || c.width <= 0 || c.grid_size <= 0 || nh <= 0 || c.patch_grid <= 0 || c.patch_grid > 255 ||
-        c.token_dim <= 0 || (c.token_dim & 3) || c.token_dim > 2048 || c.cache_size <= 0 || c.cache_size > 64 ||
-        c.iter_size <= 0 || c.iter_size > (1 << 20) || c.voxel_capacity <= 0 || c.max_points <= 0 ||
-        c.mode < 0 || c.mode > 2 || ncell >= (1ll << 31) || !(c.cell_size > 0)) {
-        bsc_set_error("bsc_create: invalid configuration (need token_dim %% 4 == 0 <= 2048, patch_grid <= 255, "
-                      "iter_size <= 2^20, gs*gs*(max_h-min_h) < 2^31)");
-        return BSC_E_INVALID;
-    }
-    BSC_HIP(hipSetDevice(device));
-    bsc_ctx *x = (bsc_ctx *)calloc(1, sizeof(bsc_ctx));
-    x->c = c;
-    x->device = device;
-    x->stream = (hipStream_t)hip_stream;
-    x->nh = (int)nh;
-    x->ncell = ncell;
-    x->g2 = c.patch_grid * c.patch_grid;
-    x->max_frames = 65535;
+    const bsc_config &c = x->c;
+    const int64_t ncell = x->ncell;
     const int64_t vcap = c.voxel_capacity, gs2 = (int64_t)c.grid_size * c.grid_size;
     const int64_t D = c.token_dim;
     const int64_t np = c.max_points > c.iter_size ? c.max_points : c.iter_size;
@@ -183,14 +149,13 @@ extern "C" bsc_status bsc_create(const bsc_config *cfg, int32_t device, void *hi
     ALLOC(x->hmap, gs2);
     ALLOC(x->cv_map, 3 * gs2);
     ALLOC(x->dscal, DS_COUNT);
-    BSC_HIP(hipHostMalloc((void **)&x->hscal, sizeof(int64_t) * (DS_COUNT + 1)));      // + a slot for the pair count read on its own
+    BSC_TRY(mem_alloc_pinned(x->mem, (void **)&x->hscal, sizeof(int64_t) * (DS_COUNT + 1), MEM_PIN_DEFAULT, "x->hscal"));   // + a slot for the pair count read on its own
     if (getenv("BSC_NO_MAILBOX") == nullptr &&
-        hipHostMalloc((void **)&x->mail, sizeof(int64_t) * (DS_COUNT + 1), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+        mem_alloc_pinned(x->mem, (void **)&x->mail, sizeof(int64_t) * (DS_COUNT + 1), MEM_PIN_MAPPED_COHERENT, "x->mail") == BSC_OK) {
         memset(x->mail, 0, sizeof(int64_t) * (DS_COUNT + 1));
-        if (hipHostGetDevicePointer((void **)&x->mail_dev, x->mail, 0) != hipSuccess) { hipHostFree(x->mail); x->mail = nullptr; }
+        if (hipHostGetDevicePointer((void **)&x->mail_dev, x->mail, 0) != hipSuccess) mem_free(x->mem, (void **)&x->mail);
     } else {
-        x->mail = nullptr;
-        (void)hipGetLastError();
+        (void)hipGetLastError();             // no mailbox: the batch scalars come through a copy
     }
     ALLOC(x->exp_tab, 128);
     {
@@ -200,7 +165,7 @@ extern "C" bsc_status bsc_create(const bsc_config *cfg, int32_t device, void *hi
             tab[2 * j] = (double)v;
             tab[2 * j + 1] = (double)(v - (long double)tab[2 * j]);
         }
-        if (hipMemcpy(x->exp_tab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) { bsc_set_error("bsc_create: exp table upload failed"); bsc_destroy(x); return BSC_E_HIP; }
+        if (hipMemcpy(x->exp_tab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) { bsc_set_error("bsc_create: exp table upload failed"); return BSC_E_HIP; }
     }
     ALLOC(x->pat_x, c.width);
     ALLOC(x->pat_y, c.height);
@@ -267,10 +232,10 @@ extern "C" bsc_status bsc_create(const bsc_config *cfg, int32_t device, void *hi
             fprintf(stderr, "bsc_create: %dx%d g=%d fast geometry %d, patch-aligned pair tiles %d\n", c.width, c.height,
                     c.patch_grid, (int)x->geom_fast, (int)x->patch_tiles);
         free(tx); free(ty);
-        if (e != hipSuccess) { bsc_set_error("bsc_create: patch tables: %s", hipGetErrorString(e)); bsc_destroy(x); return BSC_E_HIP; }
+        if (e != hipSuccess) { bsc_set_error("bsc_create: patch tables: %s", hipGetErrorString(e)); return BSC_E_HIP; }
     }
     if (c.mode == BSC_MODE_EXACT) {
-        if (c.token_capacity <= 0) { bsc_set_error("bsc_create: token_capacity"); bsc_destroy(x); return BSC_E_INVALID; }
+        if (c.token_capacity <= 0) { bsc_set_error("bsc_create: token_capacity"); return BSC_E_INVALID; }
         ALLOC(x->cache_f, (int64_t)c.iter_size * D);
         ALLOC(x->cache_pos, 3 * (int64_t)c.iter_size);
         ALLOC(x->cache_d, c.iter_size);
@@ -341,13 +306,12 @@ extern "C" bsc_status bsc_create(const bsc_config *cfg, int32_t device, void *hi
     int64_t prim_items = (np > vcap + 1) ? np : vcap + 1;
     if (x->max_tiles > prim_items) prim_items = x->max_tiles;
     x->prim_tmp_bytes = prim_workspace_bytes((size_t)prim_items);
-    hipError_t e = hipMalloc(&x->prim_tmp, x->prim_tmp_bytes);
-    if (e != hipSuccess) { bsc_set_error("hipMalloc prim workspace: %s", hipGetErrorString(e)); bsc_destroy(x); return BSC_E_HIP; }
-    e = hipMalloc(&x->prim_tmp_side, x->prim_tmp_bytes);
-    if (e != hipSuccess) { bsc_set_error("hipMalloc prim workspace: %s", hipGetErrorString(e)); bsc_destroy(x); return BSC_E_HIP; }
+    BSC_TRY(mem_alloc(x->mem, &x->prim_tmp, x->prim_tmp_bytes, "prim workspace"));
+    BSC_TRY(mem_alloc(x->mem, &x->prim_tmp_side, x->prim_tmp_bytes, "prim workspace"));
     x->order_on_side = getenv("BSC_ORDER_MAIN") == nullptr;
     x->radix_intree = getenv("BSC_SORT_ROCPRIM") == nullptr;
-    if (radix_ws_create(&x->rx_main, (size_t)prim_items) != BSC_OK || radix_ws_create(&x->rx_side, (size_t)prim_items) != BSC_OK) { bsc_destroy(x); return BSC_E_HIP; }
+    BSC_TRY(radix_ws_create(x->mem, &x->rx_main, (size_t)prim_items));
+    BSC_TRY(radix_ws_create(x->mem, &x->rx_side, (size_t)prim_items));
     BSC_HIP(hipEventCreateWithFlags(&x->ev_ids, hipEventDisableTiming));
     BSC_HIP(hipEventCreateWithFlags(&x->ev_runs, hipEventDisableTiming));
     BSC_HIP(hipEventCreateWithFlags(&x->ev_tot, hipEventDisableTiming));
@@ -356,9 +320,46 @@ extern "C" bsc_status bsc_create(const bsc_config *cfg, int32_t device, void *hi
     for (int w = 0; w < BSC_STAT_SLOTS; ++w)
         for (int i = 0; i < 2 * BSC_EV_RING; ++i) BSC_HIP(hipEventCreate(&x->ev[w][i]));
     x->timing = true;
-    bsc_status st = reset_state(x);
-    if (st != BSC_OK) { bsc_destroy(x); return st; }
+    BSC_TRY(reset_state(x));
     BSC_HIP(hipStreamSynchronize(x->stream));
+    return BSC_OK;
+}
+
+extern "C" bsc_status bsc_create(const bsc_config *cfg, int32_t device, void *hip_stream, bsc_ctx **out)
+{
+    if (!cfg || !out) { bsc_set_error("bsc_create: null argument"); return BSC_E_INVALID; }
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        bsc_set_error("bsc_create: no HIP device visible (libbscnav has no CPU path)");
+        return BSC_E_HIP;
+    }
+    if (device < 0 || device >= ndev) { bsc_set_error("bsc_create: device %d of %d", device, ndev); return BSC_E_INVALID; }
+    const bsc_config &c = *cfg;
+    const int64_t nh = (int64_t)c.max_h - c.min_h;
+    const int64_t ncell = (int64_t)c.grid_size * c.grid_size * nh;
+    if (c.height <= 0 || c.width <= 0 || c.grid_size <= 0 || nh <= 0 || c.patch_grid <= 0 || c.patch_grid > 255 ||
+        c.token_dim <= 0 || (c.token_dim & 3) || c.token_dim > 2048 || c.cache_size <= 0 || c.cache_size > 64 ||
+        c.iter_size <= 0 || c.iter_size > (1 << 20) || c.voxel_capacity <= 0 || c.max_points <= 0 ||
+        c.mode < 0 || c.mode > 2 || ncell >= (1ll << 31) || !(c.cell_size > 0)) {
+        bsc_set_error("bsc_create: invalid configuration (need token_dim %% 4 == 0 <= 2048, patch_grid <= 255, "
+                      "iter_size <= 2^20, gs*gs*(max_h-min_h) < 2^31)");
+        return BSC_E_INVALID;
+    }
+    BSC_HIP(hipSetDevice(device));
+    bsc_ctx *x = (bsc_ctx *)calloc(1, sizeof(bsc_ctx));
+    if (!x) { bsc_set_error("bsc_create: out of host memory"); return BSC_E_HIP; }
+    x->c = c;
+    x->device = device;
+    x->stream = (hipStream_t)hip_stream;
+    x->nh = (int)nh;
+    x->ncell = ncell;
+    x->g2 = c.patch_grid * c.patch_grid;
+    x->max_frames = 65535;
+    x->mem = mem_create();
+    if (!x->mem) { free(x); bsc_set_error("bsc_create: out of host memory"); return BSC_E_HIP; }
+    const bsc_status st = ctx_build(x);
+    if (st != BSC_OK) { bsc_destroy(x); return st; }      // whatever exists by now is in the ledger or null-checked there
     *out = x;
     return BSC_OK;
 }
@@ -369,31 +370,8 @@ extern "C" void bsc_destroy(bsc_ctx *x)
     hipSetDevice(x->device);
     if (x->side) hipStreamSynchronize(x->side);
     hipStreamSynchronize(x->stream);
-    surprise_ws_free(x);
-    region_ws_free(x);
-    cluster_ws_free(x);
-    void *ptrs[] = {x->exp_tab, x->pat_x, x->pat_y, x->pt_rect, x->pt_off, x->occ, x->rgb_pos, x->rgb, x->weight, x->hmap, x->cv_map, x->dscal, x->cache_f, x->cache_pos,
-                    x->cache_d, x->pool, x->pool_d, x->store_rows, x->store_cnt, x->acc, x->acnt, x->p_cell, x->p_patf,
-                    x->p_rec_s[0], x->p_rec_s[1], x->p_r2f, x->new_cells, x->run_scan, x->seg_k0, x->seg_vid, x->blk_pass, x->blk_pass_off, x->hb_cnt, x->hb_off,
-                    x->skey_a, x->sval_a, x->skey_b_s[0], x->skey_b_s[1], x->sval_b_s[0], x->sval_b_s[1], x->blk_cnt, x->blk_off,
-                    x->pstage_key, x->pstage_cnt, x->tile_cnt, x->tile_off, x->pass_list, x->seg_info_s[0], x->seg_info_s[1], x->run_val_b,
-                    x->seg_last_s[0], x->seg_last_s[1], x->bscal_s[0], x->bscal_s[1], x->f_keys_a, x->f_keys_b, x->pair_key_a, x->pair_key_b, x->pair_cnt_a, x->pair_cnt_b, x->pseg_start,
-                    x->d_transforms, x->d_offsets, x->f_rowdst, x->f_hit, x->f_hidx, x->f_rowseg, x->f_rowe,
-                    x->f_headpos, x->f_win, x->f_draws, x->l_sims, x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b,
-                    x->l_name_rank, x->l_q, x->l_qp, x->l_out_pos, x->l_out_sim, x->l_sel_key[0], x->l_sel_key[1], x->l_sel_val[0],
-                    x->l_sel_val[1], x->l_sel_thr, x->l_sel_cnt, x->l_valid, x->l_rscale, x->cp_buf[0], x->cp_buf[1], x->cp_buf[2], x->cp_buf[3], x->cp_buf[4], x->cp_buf[5], x->prim_tmp, x->prim_tmp_side, x->fr_mask, x->fr_in, x->fr_parent, x->fr_size,
-                    x->fr_ord, x->fr_roots, x->fr_labels, x->fr_first, x->fr_sizes, x->fr_scal, x->fr_sumx, x->fr_sumy,
-                    x->fr_centers, x->fr_gains, x->log_cell, x->log_rec, x->stage_cell, x->stage_pos,
-                    x->run_bits_s[0], x->run_bits_s[1], x->ck_run_s[0], x->ck_run_s[1], x->ck_start_s[0], x->ck_start_s[1], x->run_val_s[0], x->run_val_s[1]};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    for (int b = 0; b < BSC_H2D_NBUF; ++b) {
-        if (x->h2d_pin[b]) { hipHostFree(x->h2d_pin[b]); hipEventDestroy(x->h2d_ev[b]); }
-    }
-    radix_ws_destroy(&x->rx_main);
-    radix_ws_destroy(&x->rx_side);
-    if (x->hscal) hipHostFree(x->hscal);
-    if (x->mail) hipHostFree(x->mail);
+    for (int b = 0; b < BSC_H2D_NBUF; ++b)
+        if (x->h2d_ev[b]) hipEventDestroy(x->h2d_ev[b]);
     if (x->side) hipStreamDestroy(x->side);
     if (x->side2) { hipStreamSynchronize(x->side2); hipStreamDestroy(x->side2); }
     if (x->ev_chain0) hipEventDestroy(x->ev_chain0);
@@ -410,6 +388,8 @@ extern "C" void bsc_destroy(bsc_ctx *x)
     for (int w = 0; w < BSC_STAT_SLOTS; ++w)
         for (int i = 0; i < 2 * BSC_EV_RING; ++i)
             if (x->ev[w][i]) hipEventDestroy(x->ev[w][i]);
+    mem_release_all(x->mem);              // every device / pinned-host buffer of the context, the workspaces' included
+    free(x->surp); free(x->regn); free(x->clus);
     free(x);
 }
 
@@ -597,12 +577,12 @@ extern "C" bsc_status bsc_geometry(bsc_ctx *x, const float *depth_dev, const dou
 {
     if (!x || !depth_dev || !transform_host || P < 1) return BSC_E_INVALID;
     BSC_HIP(hipSetDevice(x->device));
+    MemScope temporaries(x->mem);              // released on every way out
     hipStream_t s = x->stream;
     BSC_HIP(hipMemcpyAsync(x->d_transforms, transform_host, sizeof(double) * 16, hipMemcpyHostToDevice, s));
     uint8_t *flags; double *pc, *pg, *r2, *al; int32_t *vox, *pix, *pat;
-    BSC_HIP(hipMalloc((void **)&flags, P)); BSC_HIP(hipMalloc((void **)&pc, 24 * P)); BSC_HIP(hipMalloc((void **)&pg, 24 * P));
-    BSC_HIP(hipMalloc((void **)&vox, 12 * P)); BSC_HIP(hipMalloc((void **)&pix, 8 * P)); BSC_HIP(hipMalloc((void **)&pat, 8 * P));
-    BSC_HIP(hipMalloc((void **)&r2, 8 * P)); BSC_HIP(hipMalloc((void **)&al, 8 * P));
+    ALLOC(flags, P); ALLOC(pc, 3 * P); ALLOC(pg, 3 * P); ALLOC(vox, 3 * P); ALLOC(pix, 2 * P); ALLOC(pat, 2 * P);
+    ALLOC(r2, P); ALLOC(al, P);
     BSC_HIP(hipMemsetAsync(pg, 0, 24 * P, s)); BSC_HIP(hipMemsetAsync(vox, 0, 12 * P, s));
     BSC_HIP(hipMemsetAsync(pix, 0, 8 * P, s)); BSC_HIP(hipMemsetAsync(pat, 0, 8 * P, s));
     BSC_HIP(hipMemsetAsync(r2, 0, 8 * P, s)); BSC_HIP(hipMemsetAsync(al, 0, 8 * P, s));
@@ -618,7 +598,6 @@ extern "C" bsc_status bsc_geometry(bsc_ctx *x, const float *depth_dev, const dou
         if (r2_host) hipMemcpy(r2_host, r2, 8 * P, hipMemcpyDeviceToHost);
         if (alpha_host) hipMemcpy(alpha_host, al, 8 * P, hipMemcpyDeviceToHost);
     }
-    hipFree(flags); hipFree(pc); hipFree(pg); hipFree(vox); hipFree(pix); hipFree(pat); hipFree(r2); hipFree(al);
     return st;
 }
 
@@ -808,20 +787,18 @@ extern "C" bsc_status bsc_export_store(bsc_ctx *x, int32_t *pos_host, int32_t *c
     bsc_status st = BSC_OK;
     if (nt > 0 && (feats_host || dists_host)) {
         int32_t *d_src = nullptr; float *d_out = nullptr, *d_outd = nullptr;
-        e = hipMalloc((void **)&d_src, sizeof(int32_t) * nt);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(float) * nt * D);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_outd, sizeof(float) * nt);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_src, src, sizeof(int32_t) * nt, hipMemcpyHostToDevice, x->stream);
-        if (e == hipSuccess) {
+        MemScope temporaries(x->mem);
+        st = mem_alloc(x->mem, (void **)&d_src, sizeof(int32_t) * nt, "bsc_export_store rows");
+        if (st == BSC_OK) st = mem_alloc(x->mem, (void **)&d_out, sizeof(float) * nt * D, "bsc_export_store tokens");
+        if (st == BSC_OK) st = mem_alloc(x->mem, (void **)&d_outd, sizeof(float) * nt, "bsc_export_store distances");
+        if (st == BSC_OK) e = hipMemcpyAsync(d_src, src, sizeof(int32_t) * nt, hipMemcpyHostToDevice, x->stream);
+        if (st == BSC_OK && e == hipSuccess) {
             hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((nt * 64 + TPB - 1) / TPB)), dim3(TPB), 0, x->stream, nt, d_src,
                                x->pool, x->pool_d, (int)D, d_out, d_outd);
             e = hipStreamSynchronize(x->stream);
         }
-        if (e == hipSuccess && feats_host) e = hipMemcpy(feats_host, d_out, sizeof(float) * nt * D, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && dists_host) e = hipMemcpy(dists_host, d_outd, sizeof(float) * nt, hipMemcpyDeviceToHost);
-        if (d_src) hipFree(d_src);
-        if (d_out) hipFree(d_out);
-        if (d_outd) hipFree(d_outd);
+        if (st == BSC_OK && e == hipSuccess && feats_host) e = hipMemcpy(feats_host, d_out, sizeof(float) * nt * D, hipMemcpyDeviceToHost);
+        if (st == BSC_OK && e == hipSuccess && dists_host) e = hipMemcpy(dists_host, d_outd, sizeof(float) * nt, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { bsc_set_error("bsc_export_store: %s", hipGetErrorString(e)); st = BSC_E_HIP; }
     }
     free(cnt); free(pos); free(rows); free(ents); free(src);
@@ -884,11 +861,15 @@ static bsc_status h2d_pipelined(bsc_ctx *x, void *dst_dev, const void *src_host,
         BSC_HIP(hipMemcpy(dst_dev, src_host, bytes, hipMemcpyHostToDevice));
         return BSC_OK;
     }
-    if (!x->h2d_pin[0]) {
-        for (int b = 0; b < BSC_H2D_NBUF; ++b) {
-            BSC_HIP(hipHostMalloc(&x->h2d_pin[b], BSC_H2D_CHUNK));
-            BSC_HIP(hipEventCreateWithFlags(&x->h2d_ev[b], hipEventDisableTiming));
+    if (!x->h2d_ready) {                         // the four buffers and their events, or none of the buffers
+        const uint64_t mark = mem_mark(x->mem);
+        bsc_status st = BSC_OK;
+        for (int b = 0; b < BSC_H2D_NBUF && st == BSC_OK; ++b) {
+            st = mem_alloc_pinned(x->mem, &x->h2d_pin[b], BSC_H2D_CHUNK, MEM_PIN_DEFAULT, "import staging");
+            if (st == BSC_OK && !x->h2d_ev[b] && hipEventCreateWithFlags(&x->h2d_ev[b], hipEventDisableTiming) != hipSuccess) { bsc_set_error("h2d_pipelined: hipEventCreate failed"); st = BSC_E_HIP; }
         }
+        if (st != BSC_OK) { mem_release_to(x->mem, mark); memset(x->h2d_pin, 0, sizeof x->h2d_pin); return st; }
+        x->h2d_ready = true;
     }
     int nthr = getenv("BSC_H2D_THREADS") ? atoi(getenv("BSC_H2D_THREADS")) : 8;
     const int hw = (int)std::thread::hardware_concurrency();
@@ -1000,14 +981,15 @@ extern "C" bsc_status bsc_point_log_enable(bsc_ctx *x, int64_t capacity)
     if (!x || capacity < 0) return BSC_E_INVALID;
     BSC_HIP(hipSetDevice(x->device));
     BSC_TRY(sync_all(x));
-    if (x->log_cell) { (void)hipFree(x->log_cell); x->log_cell = nullptr; }
-    if (x->log_rec) { (void)hipFree(x->log_rec); x->log_rec = nullptr; }
+    mem_free(x->mem, (void **)&x->log_cell);
+    mem_free(x->mem, (void **)&x->log_rec);
     x->log_cap = 0;
     x->log_n = 0;
     x->log_stale = false;
     if (capacity == 0) return BSC_OK;
-    BSC_HIP(hipMalloc((void **)&x->log_cell, sizeof(int32_t) * (size_t)capacity));
-    BSC_HIP(hipMalloc((void **)&x->log_rec, sizeof(PointRec) * (size_t)capacity));
+    BSC_TRY(mem_alloc(x->mem, (void **)&x->log_cell, sizeof(int32_t) * (size_t)capacity, "point log cells"));
+    const bsc_status st = mem_alloc(x->mem, (void **)&x->log_rec, sizeof(PointRec) * (size_t)capacity, "point log records");
+    if (st != BSC_OK) { mem_free(x->mem, (void **)&x->log_cell); return st; }      // both or neither: the log stays off
     x->log_cap = capacity;
     return BSC_OK;
 }
@@ -1084,6 +1066,17 @@ extern "C" bsc_status bsc_pool_query(bsc_ctx *x, const float *tokens_dev, int32_
     return pool_query_impl(x, tokens_dev, B, T, D, out_dev);
 }
 
+// scratch of both localize entries, grown on demand: similarities for every query x row, top-K staging of (position, similarity)
+static bsc_status grow_localize_scratch(bsc_ctx *x, int32_t nq, int32_t K)
+{
+    BSC_TRY(read_scalars(x));
+    const int64_t n_rows = x->c.mode == BSC_MODE_EXACT ? x->hscal[DS_POOL_N] : x->hscal[DS_MAX_ID];
+    const int64_t need = (int64_t)nq * sims_row_stride(n_rows > 0 ? n_rows : 1);
+    BSC_TRY(mem_grow(x->mem, (void **)&x->l_sims, &x->l_sims_cap, need * 4, false, "localize similarities"));
+    BSC_TRY(mem_grow(x->mem, (void **)&x->l_out_pos, &x->l_out_pos_cap, (int64_t)nq * K * 12, false, "localize top-K positions"));
+    return mem_grow(x->mem, (void **)&x->l_out_sim, &x->l_out_sim_cap, (int64_t)nq * K * 4, false, "localize top-K similarities");
+}
+
 extern "C" bsc_status bsc_localize(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, double radius,
                                    const int32_t *curr_host, int32_t floor_lo, int32_t floor_hi, int32_t *out_pos_host,
                                    float *out_sim_host, int32_t *out_count_host)
@@ -1091,22 +1084,7 @@ extern "C" bsc_status bsc_localize(bsc_ctx *x, const float *q_dev, int32_t nq, i
     if (!x || !q_dev || !out_pos_host || !out_sim_host || !out_count_host) return BSC_E_INVALID;
     if (radius >= 0 && !curr_host) { bsc_set_error("bsc_localize: region filter needs curr"); return BSC_E_INVALID; }
     BSC_HIP(hipSetDevice(x->device));
-    BSC_TRY(read_scalars(x));
-    const int64_t n_rows = x->c.mode == BSC_MODE_EXACT ? x->hscal[DS_POOL_N] : x->hscal[DS_MAX_ID];
-    const int64_t need = (int64_t)nq * sims_row_stride(n_rows > 0 ? n_rows : 1);
-    // scratch grows on demand (similarities for every query x row, top-K staging)
-    struct grow { static bsc_status run(void **p, int64_t *cap, int64_t need_bytes) {
-        if (*cap >= need_bytes) return BSC_OK;
-        if (*p) hipFree(*p);
-        *p = nullptr; *cap = 0;
-        hipError_t e = hipMalloc(p, (size_t)need_bytes);
-        if (e != hipSuccess) { bsc_set_error("bsc_localize scratch: %s", hipGetErrorString(e)); return BSC_E_HIP; }
-        *cap = need_bytes;
-        return BSC_OK;
-    } };
-    BSC_TRY(grow::run((void **)&x->l_sims, &x->l_sims_cap, need * 4));
-    BSC_TRY(grow::run((void **)&x->l_out_pos, &x->l_out_pos_cap, (int64_t)nq * K * 12));
-    BSC_TRY(grow::run((void **)&x->l_out_sim, &x->l_out_sim_cap, (int64_t)nq * K * 4));
+    BSC_TRY(grow_localize_scratch(x, nq, K));
     return localize_impl(x, q_dev, nq, K, radius, curr_host, floor_lo, floor_hi, out_pos_host, out_sim_host, out_count_host);
 }
 
@@ -1126,21 +1104,7 @@ extern "C" bsc_status bsc_localize_regions(bsc_ctx *x, const float *q_dev, int32
         }
     }
     BSC_HIP(hipSetDevice(x->device));
-    BSC_TRY(read_scalars(x));
-    const int64_t n_rows = x->c.mode == BSC_MODE_EXACT ? x->hscal[DS_POOL_N] : x->hscal[DS_MAX_ID];
-    const int64_t need = (int64_t)nq * sims_row_stride(n_rows > 0 ? n_rows : 1);
-    struct grow { static bsc_status run(void **p, int64_t *cap, int64_t need_bytes) {
-        if (*cap >= need_bytes) return BSC_OK;
-        if (*p) hipFree(*p);
-        *p = nullptr; *cap = 0;
-        hipError_t e = hipMalloc(p, (size_t)need_bytes);
-        if (e != hipSuccess) { bsc_set_error("bsc_localize_regions scratch: %s", hipGetErrorString(e)); return BSC_E_HIP; }
-        *cap = need_bytes;
-        return BSC_OK;
-    } };
-    BSC_TRY(grow::run((void **)&x->l_sims, &x->l_sims_cap, need * 4));
-    BSC_TRY(grow::run((void **)&x->l_out_pos, &x->l_out_pos_cap, (int64_t)nq * K * 12));
-    BSC_TRY(grow::run((void **)&x->l_out_sim, &x->l_out_sim_cap, (int64_t)nq * K * 4));
+    BSC_TRY(grow_localize_scratch(x, nq, K));
     return localize_regions_impl(x, q_dev, nq, K, regions_host, out_pos_host, out_sim_host, out_count_host);
 }
 

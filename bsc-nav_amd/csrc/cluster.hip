@@ -235,44 +235,16 @@ struct ClusterWs {
     int64_t pos_cap, sim_cap, out_cap, out_pin_cap;   // bytes
 };
 
-void cluster_ws_free(bsc_ctx *x)
-{
-    ClusterWs *w = x->clus;
-    if (!w) return;
-    void *ptrs[] = {w->pos, w->sim, w->cnt, w->out};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (w->out_pin) (void)hipHostFree(w->out_pin);
-    if (w->cnt_pin) (void)hipHostFree(w->cnt_pin);
-    free(w);
-    x->clus = nullptr;
-}
-
-static bsc_status cluster_grow(void **p, int64_t *cap, int64_t need_bytes, bool pinned)
-{
-    if (*cap >= need_bytes) return BSC_OK;
-    if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));     // no call is in flight: every call ends with a synchronize
-    *p = nullptr; *cap = 0;
-    const int64_t bytes = need_bytes + need_bytes / 4;
-    const hipError_t e = pinned ? hipHostMalloc(p, (size_t)bytes) : hipMalloc(p, (size_t)bytes);
-    if (e != hipSuccess) { bsc_set_error("bsc_cluster_centers workspace (%lld bytes): %s", (long long)bytes, hipGetErrorString(e)); return BSC_E_HIP; }
-    *cap = bytes;
-    return BSC_OK;
-}
-
 static bsc_status cluster_ws_get(bsc_ctx *x, ClusterWs **out)
 {
     if (!x->clus) {
         ClusterWs *w = (ClusterWs *)calloc(1, sizeof(ClusterWs));
         if (!w) { bsc_set_error("bsc_cluster_centers: out of host memory"); return BSC_E_HIP; }
-        x->clus = w;
-        hipError_t e = hipMalloc((void **)&w->cnt, sizeof(int32_t) * CL_MAXQ);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&w->cnt_pin, sizeof(int32_t) * CL_MAXQ);
-        if (e != hipSuccess) {
-            cluster_ws_free(x);
-            bsc_set_error("bsc_cluster_centers workspace: %s", hipGetErrorString(e));
-            return BSC_E_HIP;
-        }
+        const uint64_t mark = mem_mark(x->mem);
+        bsc_status st = mem_alloc(x->mem, (void **)&w->cnt, sizeof(int32_t) * CL_MAXQ, "bsc_cluster_centers counts");
+        if (st == BSC_OK) st = mem_alloc_pinned(x->mem, (void **)&w->cnt_pin, sizeof(int32_t) * CL_MAXQ, MEM_PIN_DEFAULT, "bsc_cluster_centers pinned counts");
+        if (st != BSC_OK) { mem_release_to(x->mem, mark); free(w); return st; }
+        x->clus = w;                          // published once both exist: a failed first call leaves it null
     }
     *out = x->clus;
     return BSC_OK;
@@ -291,11 +263,13 @@ static bsc_status cluster_run(bsc_ctx *x, int Q, int K, const int32_t *pos_host,
     const int64_t QK = (int64_t)Q * K;
     const int64_t off_lab = (int64_t)sizeof(double) * 3 * QK, off_siz = off_lab + (int64_t)sizeof(int32_t) * QK,
                   off_ncl = off_siz + (int64_t)sizeof(int32_t) * QK, total = off_ncl + (int64_t)sizeof(int32_t) * Q;
-    BSC_TRY(cluster_grow((void **)&w->out, &w->out_cap, total, false));
-    BSC_TRY(cluster_grow((void **)&w->out_pin, &w->out_pin_cap, total, true));
+    const char *what = "bsc_cluster_centers workspace";      // grown with 25 % slack (nothing is in flight: every call ends with a synchronize)
+    if (w->out_cap < total) BSC_TRY(mem_grow(x->mem, (void **)&w->out, &w->out_cap, total + total / 4, false, what));
+    if (w->out_pin_cap < total) BSC_TRY(mem_grow(x->mem, (void **)&w->out_pin, &w->out_pin_cap, total + total / 4, true, what));
     if (pos_host) {
-        BSC_TRY(cluster_grow((void **)&w->pos, &w->pos_cap, (int64_t)sizeof(int32_t) * 3 * QK, false));
-        BSC_TRY(cluster_grow((void **)&w->sim, &w->sim_cap, (int64_t)sizeof(float) * QK, false));
+        const int64_t pos_bytes = (int64_t)sizeof(int32_t) * 3 * QK, sim_bytes = (int64_t)sizeof(float) * QK;
+        if (w->pos_cap < pos_bytes) BSC_TRY(mem_grow(x->mem, (void **)&w->pos, &w->pos_cap, pos_bytes + pos_bytes / 4, false, what));
+        if (w->sim_cap < sim_bytes) BSC_TRY(mem_grow(x->mem, (void **)&w->sim, &w->sim_cap, sim_bytes + sim_bytes / 4, false, what));
         BSC_HIP(hipMemcpyAsync(w->pos, pos_host, sizeof(int32_t) * 3 * QK, hipMemcpyHostToDevice, s));
         BSC_HIP(hipMemcpyAsync(w->sim, sim_host, sizeof(float) * QK, hipMemcpyHostToDevice, s));
         d_pos = w->pos; d_sim = w->sim; stride = K;

@@ -523,7 +523,7 @@ bsc_status refresh_row_scales(bsc_ctx *x, const float *rows, int64_t n_rows, flo
     const int64_t need = (int64_t)sizeof(float2) * n_rows;
     if (n_rows <= 0 || x->c.token_dim % MF_KC != 0) return BSC_OK;       // cosine_scan stays off the matrix cores then
     if (!*rs_dirty && *rs && *rs_cap >= need) return BSC_OK;
-    if (*rs_cap < need) BSC_TRY(grow_dev((void **)rs, rs_cap, sizeof(float2) * (n_rows + n_rows / 8 + 1024)));
+    if (*rs_cap < need) BSC_TRY(mem_grow(x->mem, (void **)rs, rs_cap, sizeof(float2) * (n_rows + n_rows / 8 + 1024), false, "row scales"));
     hipLaunchKernelGGL(k_row_scale, dim3((unsigned)((n_rows * 64 + TPB - 1) / TPB)), dim3(TPB), 0, x->stream, rows, n_rows,
                        x->c.token_dim, *rs);
     *rs_dirty = false;

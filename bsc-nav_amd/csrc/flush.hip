@@ -139,21 +139,23 @@ bsc_status grow_token_pool(bsc_ctx *x, int64_t need)
     int64_t cap = 2 * x->c.token_capacity;
     if (cap < need) cap = need;
     float *pool = nullptr, *pool_d = nullptr;
-    hipError_t e = hipMalloc((void **)&pool, sizeof(float) * (size_t)cap * D);
-    if (e == hipSuccess) e = hipMalloc((void **)&pool_d, sizeof(float) * (size_t)cap);
-    if (e != hipSuccess) {
-        if (pool) (void)hipFree(pool);
+    const uint64_t mark = mem_mark(x->mem);
+    if (mem_alloc(x->mem, (void **)&pool, sizeof(float) * (size_t)cap * D, "token pool") != BSC_OK ||
+        mem_alloc(x->mem, (void **)&pool_d, sizeof(float) * (size_t)cap, "token pool distances") != BSC_OK) {
+        mem_release_to(x->mem, mark);
         bsc_set_error("token store: cannot grow the pool from %lld to %lld rows of %lld floats (%s)", (long long)x->c.token_capacity,
-                      (long long)cap, (long long)D, hipGetErrorString(e));
+                      (long long)cap, (long long)D, hipGetErrorString(hipErrorOutOfMemory));
         return BSC_E_CAPACITY;
     }
-    BSC_TRY(sync_all(x));                        // nothing in flight reads the old pool
-    if (x->pool_n_host > 0) {
-        BSC_HIP(hipMemcpy(pool, x->pool, sizeof(float) * (size_t)x->pool_n_host * D, hipMemcpyDeviceToDevice));
-        BSC_HIP(hipMemcpy(pool_d, x->pool_d, sizeof(float) * (size_t)x->pool_n_host, hipMemcpyDeviceToDevice));
+    bsc_status st = sync_all(x);                 // nothing in flight reads the old pool
+    if (st == BSC_OK && x->pool_n_host > 0) {
+        hipError_t e = hipMemcpy(pool, x->pool, sizeof(float) * (size_t)x->pool_n_host * D, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(pool_d, x->pool_d, sizeof(float) * (size_t)x->pool_n_host, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { bsc_set_error("token store: copy into the grown pool: %s", hipGetErrorString(e)); st = BSC_E_HIP; }
     }
-    (void)hipFree(x->pool);
-    (void)hipFree(x->pool_d);
+    if (st != BSC_OK) { mem_release_to(x->mem, mark); return st; }      // the old pool stays in charge
+    mem_free(x->mem, (void **)&x->pool);
+    mem_free(x->mem, (void **)&x->pool_d);
     x->pool = pool;
     x->pool_d = pool_d;
     x->c.token_capacity = cap;

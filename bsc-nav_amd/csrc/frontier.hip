@@ -178,18 +178,28 @@ __global__ __launch_bounds__(TPB) void k_fr_labels(int64_t n, const int32_t *__r
     labels[i] = p >= 0 ? ord[p] : -1;
 }
 
+// the frontier helpers on first use, all of them or none: fr_ready is set after the last one exists
 static bsc_status fr_alloc(bsc_ctx *x)
 {
-    if (x->fr_mask) return BSC_OK;
+    if (x->fr_ready) return BSC_OK;
     const int64_t n = (int64_t)x->c.grid_size * x->c.grid_size;
-#define FR_ALLOC(p, count) BSC_HIP(hipMalloc((void **)&(p), sizeof(*(p)) * (size_t)(count)))
-    FR_ALLOC(x->fr_mask, n); FR_ALLOC(x->fr_in, n); FR_ALLOC(x->fr_parent, n); FR_ALLOC(x->fr_size, n);
-    FR_ALLOC(x->fr_sumx, n); FR_ALLOC(x->fr_sumy, n); FR_ALLOC(x->fr_ord, n); FR_ALLOC(x->fr_roots, n);
-    FR_ALLOC(x->fr_labels, n); FR_ALLOC(x->fr_first, 2 * n); FR_ALLOC(x->fr_sizes, n);
-    FR_ALLOC(x->fr_centers, 2 * n); FR_ALLOC(x->fr_gains, n); FR_ALLOC(x->fr_scal, 2);
-#undef FR_ALLOC
-    BSC_HIP(hipMemsetAsync(x->fr_mask, 0, (size_t)n, x->stream));
-    return BSC_OK;
+#define FR_SLOT(p, count) {(void **)&(p), sizeof(*(p)) * (size_t)(count)}
+    const struct { void **slot; size_t bytes; } want[] = {
+        FR_SLOT(x->fr_mask, n), FR_SLOT(x->fr_in, n), FR_SLOT(x->fr_parent, n), FR_SLOT(x->fr_size, n), FR_SLOT(x->fr_sumx, n),
+        FR_SLOT(x->fr_sumy, n), FR_SLOT(x->fr_ord, n), FR_SLOT(x->fr_roots, n), FR_SLOT(x->fr_labels, n), FR_SLOT(x->fr_first, 2 * n),
+        FR_SLOT(x->fr_sizes, n), FR_SLOT(x->fr_centers, 2 * n), FR_SLOT(x->fr_gains, n), FR_SLOT(x->fr_scal, 2)};
+#undef FR_SLOT
+    const uint64_t mark = mem_mark(x->mem);
+    bsc_status st = BSC_OK;
+    for (const auto &a : want)
+        if (st == BSC_OK) st = mem_alloc(x->mem, a.slot, a.bytes, "frontier scratch");
+    if (st == BSC_OK && hipMemsetAsync(x->fr_mask, 0, (size_t)n, x->stream) != hipSuccess) { bsc_set_error("frontier scratch: hipMemsetAsync failed"); st = BSC_E_HIP; }
+    if (st != BSC_OK) {
+        mem_release_to(x->mem, mark);
+        for (const auto &a : want) *a.slot = nullptr;
+    }
+    x->fr_ready = st == BSC_OK;
+    return st;
 }
 
 bsc_status frontier_mask_impl(bsc_ctx *x, const uint8_t *navigable_host, uint8_t *mask_host)

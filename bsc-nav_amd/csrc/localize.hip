@@ -557,17 +557,6 @@ __global__ void k_sel_check(const u64 *__restrict__ thr, const int32_t *__restri
 #endif
 }
 
-bsc_status grow_dev(void **p, int64_t *cap, int64_t need_bytes)
-{
-    if (*cap >= need_bytes) return BSC_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    hipError_t e = hipMalloc(p, (size_t)need_bytes);
-    if (e != hipSuccess) { bsc_set_error("bsc_localize scratch (%lld bytes): %s", (long long)need_bytes, hipGetErrorString(e)); return BSC_E_HIP; }
-    *cap = need_bytes;
-    return BSC_OK;
-}
-
 // K <= 512, all queries at once, no device-wide sort:
 //   small candidate sets: rounds of 1024-key bitonic selections (round 1 fused with the candidate scan);
 //   large sets: selection over a sample of 16 blocks spread over the map gives a per-query threshold, one streaming filter
@@ -608,12 +597,12 @@ static bsc_status select_topk_batched(bsc_ctx *x, const A &ca, int nq, int64_t s
     const int64_t nbs = use_filter ? nbs_want : nb1;
     int64_t stride = nbs * K;
     if (use_filter && stride < SEL_SURVIVOR_CAP) stride = SEL_SURVIVOR_CAP;
-    BSC_TRY(grow_dev((void **)&x->l_sel_key[0], &x->l_sel_cap[0], sizeof(u64) * stride * nq));
-    BSC_TRY(grow_dev((void **)&x->l_sel_key[1], &x->l_sel_cap[1], sizeof(u64) * stride * nq));
-    BSC_TRY(grow_dev((void **)&x->l_sel_val[0], &x->l_sel_cap[2], sizeof(uint32_t) * stride * nq));
-    BSC_TRY(grow_dev((void **)&x->l_sel_val[1], &x->l_sel_cap[3], sizeof(uint32_t) * stride * nq));
-    BSC_TRY(grow_dev((void **)&x->l_sel_thr, &x->l_sel_cap[4], sizeof(u64) * (int64_t)(nq + 1)));
-    BSC_TRY(grow_dev((void **)&x->l_sel_cnt, &x->l_sel_cap[5], sizeof(int32_t) * nq * SEL_CNT_PAD));
+    BSC_TRY(mem_grow(x->mem, (void **)&x->l_sel_key[0], &x->l_sel_cap[0], sizeof(u64) * stride * nq, false, "localize selection scratch"));
+    BSC_TRY(mem_grow(x->mem, (void **)&x->l_sel_key[1], &x->l_sel_cap[1], sizeof(u64) * stride * nq, false, "localize selection scratch"));
+    BSC_TRY(mem_grow(x->mem, (void **)&x->l_sel_val[0], &x->l_sel_cap[2], sizeof(uint32_t) * stride * nq, false, "localize selection scratch"));
+    BSC_TRY(mem_grow(x->mem, (void **)&x->l_sel_val[1], &x->l_sel_cap[3], sizeof(uint32_t) * stride * nq, false, "localize selection scratch"));
+    BSC_TRY(mem_grow(x->mem, (void **)&x->l_sel_thr, &x->l_sel_cap[4], sizeof(u64) * (int64_t)(nq + 1), false, "localize selection scratch"));
+    BSC_TRY(mem_grow(x->mem, (void **)&x->l_sel_cnt, &x->l_sel_cap[5], sizeof(int32_t) * nq * SEL_CNT_PAD, false, "localize selection scratch"));
     int cur = 0;
     // round 1 over the sample (or over everything), fused with the candidate keys
     hipLaunchKernelGGL(k_cand_topk<A>, dim3((unsigned)(nbs * nq < 4096 ? nbs * nq : 4096)), dim3(TPB), 0, x->stream, ca, x->l_sims,
@@ -631,7 +620,7 @@ static bsc_status select_topk_batched(bsc_ctx *x, const A &ca, int nq, int64_t s
             // slack (a map that gains a few voxels between two queries keeps its bitmap allocation)
             const int64_t words = (TPB / 32) * (((int64_t)ca.max_id + TPB - 1) / TPB) + 2;
             if ((int64_t)sizeof(uint32_t) * words > x->l_sel_cap[6])
-                BSC_TRY(grow_dev((void **)&x->l_valid, &x->l_sel_cap[6], sizeof(uint32_t) * (words + words / 4 + 1024)));
+                BSC_TRY(mem_grow(x->mem, (void **)&x->l_valid, &x->l_sel_cap[6], sizeof(uint32_t) * (words + words / 4 + 1024), false, "localize row bitmap"));
             if (ca.max_id > 0)
                 hipLaunchKernelGGL(k_valid_bits, dim3((unsigned)((ca.max_id + TPB - 1) / TPB)), dim3(TPB), 0, x->stream, ca.cnt, ca.max_id, x->l_valid);
         }
@@ -804,28 +793,17 @@ struct RegionWs {
 #define BSC_REGION_PRUNE_SHARE 0.33
 #endif
 
-void region_ws_free(bsc_ctx *x)
-{
-    RegionWs *w = x->regn;
-    if (!w) return;
-    void *ptrs[] = {w->regions, w->mask, w->vis, w->blk_tot, w->blk_off, w->cidx, w->rowoff, w->rows, w->rscale};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (w->regions_pin) (void)hipHostFree(w->regions_pin);
-    if (w->tot_pin) (void)hipHostFree(w->tot_pin);
-    free(w);
-    x->regn = nullptr;
-}
-
 static bsc_status region_ws_get(bsc_ctx *x, RegionWs **out)
 {
     if (!x->regn) {
         RegionWs *w = (RegionWs *)calloc(1, sizeof(RegionWs));
         if (!w) { bsc_set_error("bsc_localize_regions: out of host memory"); return BSC_E_HIP; }
-        x->regn = w;
-        BSC_HIP(hipMalloc((void **)&w->regions, sizeof(RegionDev) * 1024));
-        BSC_HIP(hipHostMalloc((void **)&w->regions_pin, sizeof(RegionDev) * 1024));
-        BSC_HIP(hipHostMalloc((void **)&w->tot_pin, sizeof(int64_t)));
+        const uint64_t mark = mem_mark(x->mem);
+        bsc_status st = mem_alloc(x->mem, (void **)&w->regions, sizeof(RegionDev) * 1024, "regions");
+        if (st == BSC_OK) st = mem_alloc_pinned(x->mem, (void **)&w->regions_pin, sizeof(RegionDev) * 1024, MEM_PIN_DEFAULT, "pinned regions");
+        if (st == BSC_OK) st = mem_alloc_pinned(x->mem, (void **)&w->tot_pin, sizeof(int64_t), MEM_PIN_DEFAULT, "pinned region totals");
+        if (st != BSC_OK) { mem_release_to(x->mem, mark); free(w); return st; }
+        x->regn = w;                          // published once all of it exists: a failed first call leaves it null
     }
     *out = x->regn;
     return BSC_OK;
@@ -949,11 +927,11 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
     if (pass) {
         const int nwords = (nq + 31) / 32;
         if (w->mask_cap < (int64_t)sizeof(uint32_t) * mask_stride * nwords)
-            BSC_TRY(grow_dev((void **)&w->mask, &w->mask_cap, sizeof(uint32_t) * (mask_stride + mask_stride / 8 + 1024) * nwords));
-        if (w->vis_cap < n_cand) BSC_TRY(grow_dev((void **)&w->vis, &w->vis_cap, n_cand + n_cand / 8 + 1024));
+            BSC_TRY(mem_grow(x->mem, (void **)&w->mask, &w->mask_cap, sizeof(uint32_t) * (mask_stride + mask_stride / 8 + 1024) * nwords, false, "region scratch"));
+        if (w->vis_cap < n_cand) BSC_TRY(mem_grow(x->mem, (void **)&w->vis, &w->vis_cap, n_cand + n_cand / 8 + 1024, false, "region scratch"));
         if (w->blk_cap[0] < (int64_t)sizeof(int64_t) * (nblk + 1)) {
-            BSC_TRY(grow_dev((void **)&w->blk_tot, &w->blk_cap[0], sizeof(int64_t) * (nblk + nblk / 8 + 64)));
-            BSC_TRY(grow_dev((void **)&w->blk_off, &w->blk_cap[1], sizeof(int64_t) * (nblk + nblk / 8 + 64)));
+            BSC_TRY(mem_grow(x->mem, (void **)&w->blk_tot, &w->blk_cap[0], sizeof(int64_t) * (nblk + nblk / 8 + 64), false, "region scratch"));
+            BSC_TRY(mem_grow(x->mem, (void **)&w->blk_off, &w->blk_cap[1], sizeof(int64_t) * (nblk + nblk / 8 + 64), false, "region scratch"));
         }
         BSC_HIP(hipMemsetAsync(w->blk_tot + nblk, 0, sizeof(int64_t), s));           // the scan's last output is the total
         hipLaunchKernelGGL(k_region_visibility, dim3(nblk), block, 0, s, n_cand, v.max_id, v.vcap, v.exact, v.rgb_pos, v.cnt,
@@ -983,11 +961,11 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
     bool scratch_dirty = true, *rs_dirty = &x->row_scale_dirty;
     if (pruned) {
         if (w->cidx_cap < (int64_t)sizeof(uint32_t) * n_vis) {
-            BSC_TRY(grow_dev((void **)&w->cidx, &w->cidx_cap, sizeof(uint32_t) * (n_vis + n_vis / 4 + 1024)));
-            BSC_TRY(grow_dev((void **)&w->rowoff, &w->rowoff_cap, sizeof(int32_t) * (n_vis + n_vis / 4 + 1024)));
+            BSC_TRY(mem_grow(x->mem, (void **)&w->cidx, &w->cidx_cap, sizeof(uint32_t) * (n_vis + n_vis / 4 + 1024), false, "region scratch"));
+            BSC_TRY(mem_grow(x->mem, (void **)&w->rowoff, &w->rowoff_cap, sizeof(int32_t) * (n_vis + n_vis / 4 + 1024), false, "region scratch"));
         }
         if (w->rows_cap < (int64_t)sizeof(float) * n_vis_rows * D)
-            BSC_TRY(grow_dev((void **)&w->rows, &w->rows_cap, sizeof(float) * (n_vis_rows + n_vis_rows / 4 + 1024) * D));
+            BSC_TRY(mem_grow(x->mem, (void **)&w->rows, &w->rows_cap, sizeof(float) * (n_vis_rows + n_vis_rows / 4 + 1024) * D, false, "region scratch"));
         hipLaunchKernelGGL(k_region_scatter, dim3(nblk), block, 0, s, n_cand, v.max_id, v.vcap, v.exact, v.cnt,
                            (const uint8_t *)w->vis, (const int64_t *)w->blk_off, w->cidx, w->rowoff);
         hipLaunchKernelGGL(k_region_gather_rows, dim3((unsigned)((n_vis * 64 + TPB - 1) / TPB)), block, 0, s, (int)n_vis, v.max_id, v.vcap,

@@ -312,28 +312,20 @@ bsc_status radix_sort_pairs_u32(bsc_ctx *x, RadixWs *ws, hipStream_t st, const u
     return BSC_OK;
 }
 
-bsc_status radix_ws_create(RadixWs *ws, size_t max_items)
+bsc_status radix_ws_create(BscMem *m, RadixWs *ws, size_t max_items)
 {
     memset(ws, 0, sizeof *ws);
     ws->max_items = max_items;
     const size_t tiles = (max_items + RX_TILE - 1) / RX_TILE + 1;
-    BSC_HIP(hipMalloc((void **)&ws->status, tiles * RX_BINS * sizeof(u64)));
+    BSC_TRY(mem_alloc(m, (void **)&ws->status, tiles * RX_BINS * sizeof(u64), "radix status"));
     BSC_HIP(hipMemset(ws->status, 0, tiles * RX_BINS * sizeof(u64)));
-    BSC_HIP(hipMalloc((void **)&ws->partial, (size_t)RX_HIST_BLOCKS * 4 * RX_BINS * 4));
-    BSC_HIP(hipMalloc((void **)&ws->goff, 4 * RX_BINS * 4));
-    BSC_HIP(hipMalloc((void **)&ws->gpartial, (size_t)(RX_HIST_BLOCKS / RX_HGROUP) * 4 * RX_BINS * 4));
-    BSC_HIP(hipMalloc((void **)&ws->tickets, 4 * (8 + RX_HIST_BLOCKS / RX_HGROUP)));
+    BSC_TRY(mem_alloc(m, (void **)&ws->partial, (size_t)RX_HIST_BLOCKS * 4 * RX_BINS * 4, "radix partials"));
+    BSC_TRY(mem_alloc(m, (void **)&ws->goff, 4 * RX_BINS * 4, "radix offsets"));
+    BSC_TRY(mem_alloc(m, (void **)&ws->gpartial, (size_t)(RX_HIST_BLOCKS / RX_HGROUP) * 4 * RX_BINS * 4, "radix group partials"));
+    BSC_TRY(mem_alloc(m, (void **)&ws->tickets, 4 * (8 + RX_HIST_BLOCKS / RX_HGROUP), "radix tickets"));
     BSC_HIP(hipMemset(ws->tickets, 0, 4 * (8 + RX_HIST_BLOCKS / RX_HGROUP)));
-    BSC_HIP(hipMalloc((void **)&ws->tmp_k, 4 * max_items));
-    BSC_HIP(hipMalloc((void **)&ws->tmp_v, 4 * max_items));
+    BSC_TRY(mem_alloc(m, (void **)&ws->tmp_k, 4 * max_items, "radix keys"));
+    BSC_TRY(mem_alloc(m, (void **)&ws->tmp_v, 4 * max_items, "radix values"));
     ws->epoch = 0;
     return BSC_OK;
-}
-
-void radix_ws_destroy(RadixWs *ws)
-{
-    void *ptrs[] = {ws->status, ws->partial, ws->gpartial, ws->goff, ws->tickets, ws->tmp_k, ws->tmp_v};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    memset(ws, 0, sizeof *ws);
 }

@@ -129,9 +129,9 @@ bsc_status compact_store_impl(bsc_ctx *x, int64_t live_known, int64_t *rows_befo
         struct { uint8_t *mark; int64_t *blk_tot, *blk_off; int32_t *holes, *movers, *remap; } w;
         const int64_t nblk = (pool_n + TPB - 1) / TPB, n_slots = (vcap + 1) * cs;
         const dim3 block(TPB), rgrid((unsigned)nblk), sgrid((unsigned)((n_slots + TPB - 1) / TPB));
-        BSC_TRY(grow_dev(&x->cp_buf[0], &x->cp_cap[0], pool_n + pool_n / 8 + 1024));
-        BSC_TRY(grow_dev(&x->cp_buf[1], &x->cp_cap[1], (int64_t)sizeof(int64_t) * (nblk + nblk / 8 + 64)));
-        BSC_TRY(grow_dev(&x->cp_buf[2], &x->cp_cap[2], (int64_t)sizeof(int64_t) * (nblk + nblk / 8 + 64)));
+        BSC_TRY(mem_grow(x->mem, &x->cp_buf[0], &x->cp_cap[0], pool_n + pool_n / 8 + 1024, false, "compaction scratch"));
+        BSC_TRY(mem_grow(x->mem, &x->cp_buf[1], &x->cp_cap[1], (int64_t)sizeof(int64_t) * (nblk + nblk / 8 + 64), false, "compaction scratch"));
+        BSC_TRY(mem_grow(x->mem, &x->cp_buf[2], &x->cp_cap[2], (int64_t)sizeof(int64_t) * (nblk + nblk / 8 + 64), false, "compaction scratch"));
         w.mark = (uint8_t *)x->cp_buf[0];
         w.blk_tot = (int64_t *)x->cp_buf[1];
         w.blk_off = (int64_t *)x->cp_buf[2];
@@ -152,9 +152,9 @@ bsc_status compact_store_impl(bsc_ctx *x, int64_t live_known, int64_t *rows_befo
         if (M > 0) {
             // the cached scales move with their rows when they are current (cosine_scan.hip refresh_row_scales)
             const bool scales = !x->row_scale_dirty && x->l_rscale && x->l_rscale_cap >= (int64_t)sizeof(float2) * pool_n;
-            BSC_TRY(grow_dev(&x->cp_buf[3], &x->cp_cap[3], (int64_t)sizeof(int32_t) * (M + M / 8 + 1024)));
-            BSC_TRY(grow_dev(&x->cp_buf[4], &x->cp_cap[4], (int64_t)sizeof(int32_t) * (M + M / 8 + 1024)));
-            BSC_TRY(grow_dev(&x->cp_buf[5], &x->cp_cap[5], (int64_t)sizeof(int32_t) * (pool_n - L + (pool_n - L) / 8 + 1024)));
+            BSC_TRY(mem_grow(x->mem, &x->cp_buf[3], &x->cp_cap[3], (int64_t)sizeof(int32_t) * (M + M / 8 + 1024), false, "compaction scratch"));
+            BSC_TRY(mem_grow(x->mem, &x->cp_buf[4], &x->cp_cap[4], (int64_t)sizeof(int32_t) * (M + M / 8 + 1024), false, "compaction scratch"));
+            BSC_TRY(mem_grow(x->mem, &x->cp_buf[5], &x->cp_cap[5], (int64_t)sizeof(int32_t) * (pool_n - L + (pool_n - L) / 8 + 1024), false, "compaction scratch"));
             w.holes = (int32_t *)x->cp_buf[3];
             w.movers = (int32_t *)x->cp_buf[4];
             w.remap = (int32_t *)x->cp_buf[5];

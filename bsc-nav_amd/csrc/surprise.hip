@@ -44,53 +44,29 @@ struct SurpriseWs {
     int32_t *scal;                  // [0] tasks [1] task voxels [2] levels
 };
 
-static bsc_status ws_alloc(void **p, size_t bytes)
-{
-    BSC_HIP(hipMalloc(p, bytes ? bytes : 4));
-    return BSC_OK;
-}
-
-void surprise_ws_free(bsc_ctx *x)
-{
-    SurpriseWs *w = x->surp;
-    if (!w) return;
-    void *ptrs[] = {w->ent, w->head, w->tid, w->first, w->dense, w->tstart, w->tent, w->lvl, w->order, w->cid, w->nb,
-                    w->lcnt, w->loff, w->lvtab, w->inv, w->acc, w->scal};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    free(w);
-    x->surp = nullptr;
-}
-
-// scratch on the first call (bsc_create allocates nothing for this path); the neighbour lists grow with the radius
+// scratch on the first call (bsc_create allocates nothing for this path), all of it or none: x->surp is published once every
+// buffer exists.  The neighbour lists grow with the radius; a failed regrow leaves k_cap == 0 and the next call tries again.
 static bsc_status ws_ensure(bsc_ctx *x, int K)
 {
     const int64_t n = x->c.iter_size, vcap = x->c.voxel_capacity;
-    if (!x->surp) {
-        SurpriseWs *w = (SurpriseWs *)calloc(1, sizeof(SurpriseWs));
-        x->surp = w;
-        BSC_TRY(ws_alloc((void **)&w->ent, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->head, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->tid, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->first, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->dense, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->tstart, sizeof(int32_t) * (n + 1)));
-        BSC_TRY(ws_alloc((void **)&w->tent, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->lvl, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->order, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->cid, sizeof(int32_t) * (vcap + 1)));
-        BSC_TRY(ws_alloc((void **)&w->lcnt, sizeof(int32_t) * (n + 2)));
-        BSC_TRY(ws_alloc((void **)&w->loff, sizeof(int32_t) * (n + 2)));
-        BSC_TRY(ws_alloc((void **)&w->inv, sizeof(float) * n));
-        BSC_TRY(ws_alloc((void **)&w->acc, sizeof(int32_t) * n));
-        BSC_TRY(ws_alloc((void **)&w->scal, sizeof(int32_t) * 4));
-    }
     SurpriseWs *w = x->surp;
+    if (!w) {
+        w = (SurpriseWs *)calloc(1, sizeof(SurpriseWs));
+        if (!w) { bsc_set_error("bsc_flush_surprise: out of host memory"); return BSC_E_HIP; }
+        const struct { int32_t **slot; int64_t count; } want[] = {
+            {&w->ent, n}, {&w->head, n}, {&w->tid, n}, {&w->first, n}, {&w->dense, n}, {&w->tstart, n + 1}, {&w->tent, n}, {&w->lvl, n},
+            {&w->order, n}, {&w->cid, vcap + 1}, {&w->lcnt, n + 2}, {&w->loff, n + 2}, {(int32_t **)&w->inv, n}, {&w->acc, n}, {&w->scal, 4}};
+        const uint64_t mark = mem_mark(x->mem);
+        for (const auto &a : want) {             // every one is 4 bytes per element (inv: float)
+            const bsc_status st = mem_alloc(x->mem, (void **)a.slot, sizeof(int32_t) * (size_t)a.count, "surprise flush scratch");
+            if (st != BSC_OK) { mem_release_to(x->mem, mark); free(w); return st; }
+        }
+        x->surp = w;
+    }
     if (w->k_cap < K) {
-        if (w->nb) (void)hipFree(w->nb);
-        w->nb = nullptr;
+        mem_free(x->mem, (void **)&w->nb);
         w->k_cap = 0;
-        BSC_TRY(ws_alloc((void **)&w->nb, sizeof(int32_t) * (size_t)n * K));
+        BSC_TRY(mem_alloc(x->mem, (void **)&w->nb, sizeof(int32_t) * (size_t)n * K, "surprise flush neighbour lists"));
         w->k_cap = K;
     }
     return BSC_OK;
@@ -700,7 +676,7 @@ bsc_status surprise_flush(bsc_ctx *x, int32_t radius, double sthr, double bthr)
         hipLaunchKernelGGL((k_surp_levels<uint32_t, SURP_TAB32>), dim3(1), dim3(64), 0, s, n_u, n_tasks, K, ws->nb, ws->lvl,
                            ws->lcnt, ws->scal);
     else {
-        if (!ws->lvtab) BSC_TRY(ws_alloc((void **)&ws->lvtab, sizeof(int32_t) * (size_t)n));
+        if (!ws->lvtab) BSC_TRY(mem_alloc(x->mem, (void **)&ws->lvtab, sizeof(int32_t) * (size_t)n, "surprise flush level table"));
         hipLaunchKernelGGL(k_surp_levels_global, dim3(1), dim3(64), 0, s, ws->lvtab, n_u, n_tasks, K, ws->nb, ws->lvl, ws->lcnt,
                            ws->scal);
     }
