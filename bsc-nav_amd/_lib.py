@@ -67,6 +67,7 @@ SIGNATURES = {
     "bsc_pool_query": (_I32, [_VP, _VP, _I32, _I32, _I32, _VP]),
     "bsc_localize": (_I32, [_VP, _VP, _I32, _I32, _F64, _VP, _I32, _I32, _VP, _VP, _VP]),
     "bsc_localize_regions": (_I32, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "bsc_score_map": (_I32, [_VP, _VP, _I32, _VP, _VP, _VP]),
     "bsc_cluster_centers": (_I32, [_VP, _I32, _I32, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
     "bsc_cluster_centers_batch": (_I32, [_VP, _I32, _I32, _VP, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
     "bsc_frontier_mask": (_I32, [_VP, _VP, _VP]),

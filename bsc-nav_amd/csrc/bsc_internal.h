@@ -213,6 +213,8 @@ struct bsc_ctx {
     int last_nq, last_K;            // shape of the last bsc_localize / bsc_localize_regions call (its top-K stays resident for clustering)
     RegionWs *regn;                 // bsc_localize_regions scratch (nullptr until its first call)
     int32_t last_counts[1024];
+    u64 *sm_map;                    // bsc_score_map scratch: packed (score, height) keys of one chunk of queries (score_map.hip)
+    int64_t sm_cap;                 // bytes
     ClusterWs *clus;                // bsc_cluster_centers / bsc_cluster_centers_batch workspace (nullptr until the first call)
     // frontier helpers (allocated on first use, gs*gs each)
     bool fr_ready;             // all of them exist (frontier.hip fr_alloc)
@@ -373,6 +375,13 @@ bsc_status localize_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, 
                          int32_t floor_lo, int32_t floor_hi, int32_t *out_pos, float *out_sim, int32_t *out_count);
 bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, const bsc_region *regions,
                                  int32_t *out_pos, float *out_sim, int32_t *out_count);
+// The front half of bsc_localize_regions, which bsc_score_map shares (localize.hip; RegionScan: localize_cand.h): region staging,
+// the visibility pass, the pruning decision, the row gather and the cosine scan of nq queries -> x->l_sims and the candidate list
+// (RegionCandArgs) that reads it.  regions == nullptr: no region for any query.
+struct RegionScan;
+BSC_LOCAL bsc_status region_scan(bsc_ctx *x, const float *q_dev, int32_t nq, const bsc_region *regions, RegionScan *out);
+// bsc_score_map behind its argument checks (score_map.hip)
+bsc_status score_map_impl(bsc_ctx *x, const float *q_dev, int32_t nq, const bsc_region *regions, float *score_dev, int32_t *height_dev);
 // ---- the cosine scan (cosine_scan.hip), as localize.hip calls it ----
 int64_t sims_row_stride(int64_t n_rows);   // floats between the similarity rows of consecutive queries
 // q_dev (nq, D) -> x->l_q: normalised, zero-padded to the whole query tiles the matrix-core kernels read

@@ -1066,13 +1066,19 @@ extern "C" bsc_status bsc_pool_query(bsc_ctx *x, const float *tokens_dev, int32_
     return pool_query_impl(x, tokens_dev, B, T, D, out_dev);
 }
 
-// scratch of both localize entries, grown on demand: similarities for every query x row, top-K staging of (position, similarity)
-static bsc_status grow_localize_scratch(bsc_ctx *x, int32_t nq, int32_t K)
+// similarities for every query x row, grown on demand
+static bsc_status grow_localize_sims(bsc_ctx *x, int32_t nq)
 {
     BSC_TRY(read_scalars(x));
     const int64_t n_rows = x->c.mode == BSC_MODE_EXACT ? x->hscal[DS_POOL_N] : x->hscal[DS_MAX_ID];
     const int64_t need = (int64_t)nq * sims_row_stride(n_rows > 0 ? n_rows : 1);
-    BSC_TRY(mem_grow(x->mem, (void **)&x->l_sims, &x->l_sims_cap, need * 4, false, "localize similarities"));
+    return mem_grow(x->mem, (void **)&x->l_sims, &x->l_sims_cap, need * 4, false, "localize similarities");
+}
+
+// scratch of both localize entries, grown on demand: the similarities, top-K staging of (position, similarity)
+static bsc_status grow_localize_scratch(bsc_ctx *x, int32_t nq, int32_t K)
+{
+    BSC_TRY(grow_localize_sims(x, nq));
     BSC_TRY(mem_grow(x->mem, (void **)&x->l_out_pos, &x->l_out_pos_cap, (int64_t)nq * K * 12, false, "localize top-K positions"));
     return mem_grow(x->mem, (void **)&x->l_out_sim, &x->l_out_sim_cap, (int64_t)nq * K * 4, false, "localize top-K similarities");
 }
@@ -1106,6 +1112,22 @@ extern "C" bsc_status bsc_localize_regions(bsc_ctx *x, const float *q_dev, int32
     BSC_HIP(hipSetDevice(x->device));
     BSC_TRY(grow_localize_scratch(x, nq, K));
     return localize_regions_impl(x, q_dev, nq, K, regions_host, out_pos_host, out_sim_host, out_count_host);
+}
+
+extern "C" bsc_status bsc_score_map(bsc_ctx *x, const float *q_dev, int32_t nq, const bsc_region *regions_host, float *score_dev,
+                                    int32_t *height_dev)
+{
+    if (!x || !q_dev || !score_dev) return BSC_E_INVALID;
+    if (nq < 1 || nq > 1024) { bsc_set_error("bsc_score_map: n_queries=%d (1..1024)", nq); return BSC_E_INVALID; }
+    for (int32_t i = 0; regions_host && i < nq; ++i) {
+        if (regions_host[i].radius != regions_host[i].radius || regions_host[i].reserved != 0) {
+            bsc_set_error("bsc_score_map: region %d: radius is NaN or reserved != 0", i);
+            return BSC_E_INVALID;
+        }
+    }
+    BSC_HIP(hipSetDevice(x->device));
+    BSC_TRY(grow_localize_sims(x, nq));      // (the top-K staging, where the last localize call's results live, is left alone)
+    return score_map_impl(x, q_dev, nq, regions_host, score_dev, height_dev);
 }
 
 // ---- multi-GPU merge helpers (dense modes) ---------------------------------------------------------------

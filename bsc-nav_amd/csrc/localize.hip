@@ -12,6 +12,7 @@
 //   k_region_*     bsc_localize_regions (end of this file): a sphere and floor band per query (BSCAgent.py:630-647,1078-1098),
 //                  visibility pass, compaction + gather of the visible rows, the scan over those rows only
 #include "bsc_internal.h"
+#include "localize_cand.h"
 
 #include <math.h>
 #include <type_traits>
@@ -69,13 +70,6 @@ __global__ __launch_bounds__(TPB) void k_pool_query(const float *__restrict__ to
     out[d] = total / (float)B;
 }
 
-__device__ __forceinline__ uint32_t float_desc_key(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // ascending-orderable
-    return ~u;                                          // descending similarity == ascending key
-}
-
 // candidate c in [0, n_cand): c < max_id is voxel id c, c == max_id is the grid_0_0_0 group (entry vcap)
 __global__ __launch_bounds__(TPB) void k_name_keys(int n_cand, int max_id, int vcap, const int32_t *__restrict__ rgb_pos,
                                                    const int32_t *__restrict__ cnt, u64 *__restrict__ keys,
@@ -98,32 +92,7 @@ __global__ __launch_bounds__(TPB) void k_name_rank(int n_cand, const uint32_t *_
     rank[sorted_vals[i]] = (uint32_t)i;
 }
 
-// ---- the candidates of the selection ------------------------------------------------------------------------------------------
-// The store as the candidate kernels read it, whatever its mode.  Candidate (voxel) c in [0, max_id] sits in entry c of cnt /
-// rgb_pos / store_rows, except c == max_id, the grid_0_0_0 group: entry vcap, position (0, 0, 0).  (Dense acnt has no slot of its
-// own for that group: it is allocated vcap + 1.)
-struct VoxelView {
-    int max_id, vcap, cache_size, exact;
-    const int32_t *rgb_pos, *cnt, *store_rows;
-    const uint32_t *name_rank;
-
-    __device__ __forceinline__ int entry(int c) const { return (c == max_id) ? vcap : c; }
-    __device__ __forceinline__ void position(int c, int &r, int &cc, int &h) const
-    {
-        r = 0; cc = 0; h = 0;
-        if (c != max_id) { r = rgb_pos[3 * c]; cc = rgb_pos[3 * c + 1]; h = rgb_pos[3 * c + 2]; }
-    }
-    // similarity key of the best of the m tokens of entry e (memory_2.py:661) when the scan ran over the store's own rows: token-pool
-    // rows of an exact store, row e of a dense map
-    __device__ __forceinline__ float best_sim(int e, int m, const float *__restrict__ sims) const
-    {
-        if (!exact) return sims[e];
-        float best = -INFINITY;
-        for (int k = 0; k < m; ++k) best = fmaxf(best, sims[store_rows[(int64_t)e * cache_size + k]]);
-        return best;
-    }
-};
-
+// ---- the candidates of the selection (VoxelView, RegionDev, CandArgs / RegionCandArgs: localize_cand.h) --------------------------
 // what the context's store holds now (read_scalars first): the view, and through the pointers the candidates (max_id + 1) and the
 // matrix the scan reads
 static VoxelView store_view(const bsc_ctx *x, int *n_cand, int64_t *n_rows, const float **rows)
@@ -138,59 +107,14 @@ static VoxelView store_view(const bsc_ctx *x, int *n_cand, int64_t *n_rows, cons
     return v;
 }
 
-// bsc_region as the kernels read it: radius^2 in double, the two switches resolved
-struct RegionDev {
-    double radius2;
-    int32_t c0, c1, c2, floor_lo, floor_hi, use_radius;
-};
-static_assert(sizeof(RegionDev) == 32, "RegionDev layout");
-
 static RegionDev region_dev(double radius, const int32_t *curr, int32_t floor_lo, int32_t floor_hi)
 {
     return RegionDev{radius * radius, curr ? curr[0] : 0, curr ? curr[1] : 0, curr ? curr[2] : 0, floor_lo, floor_hi, radius >= 0 ? 1 : 0};
 }
 
-// neither sphere nor floor band: the region holds every voxel
-__host__ __device__ static inline bool region_open(const RegionDev &g) { return !g.use_radius && !(g.floor_lo <= g.floor_hi); }
-
-// memory_2.py:624-640 for one voxel and one region
-__device__ __forceinline__ bool region_sees(const RegionDev &g, int r, int cc, int h)
-{
-    if (g.use_radius) {   // :624-629 (integer squared distance compared with radius**2)
-        const double dx = r - g.c0, dy = cc - g.c1, dz = h - g.c2;
-        if (!((dx * dx + dy * dy + dz * dz) <= g.radius2)) return false;
-    }
-    if (g.floor_lo <= g.floor_hi && !((g.floor_lo <= h) && (h <= g.floor_hi))) return false;   // :633-640
-    return true;
-}
-
-// The selection kernels below are written once for two kinds of candidate list: CandArgs (bsc_localize: every voxel, one region
-// for all queries) and RegionCandArgs (bsc_localize_regions: a region per query, possibly a compacted list).  Entry i of a list
-// has a similarity key for query q (0xffffffff: filtered out / empty), a voxel (what k_gather_topk reads the position of) and a
-// name rank.
-struct CandArgs : VoxelView {
-    int n_cand;                    // max_id + 1
-    RegionDev region;
-};
-
-struct RegionCandArgs : VoxelView {
-    int n_cand;                    // entries of the list: max_id + 1, or the visible voxels when the scan was pruned
-    const RegionDev *regions;      // (Q)
-    const uint32_t *mask;          // visibility bits, word (q / 32) * mask_stride + voxel; nullptr: the pass was skipped
-    int64_t mask_stride;
-    const uint32_t *cidx;          // pruned scan: entry -> voxel (candidate id); nullptr: entry i is voxel i
-    const int32_t *rowoff;         // pruned scan: entry -> its first row in the gathered matrix
-};
-
 static CandArgs cand_args(const VoxelView &v, int n_cand, const RegionDev &region) { return CandArgs{v, n_cand, region}; }
 // every voxel for every query
 static CandArgs cand_args_open(const VoxelView &v, int n_cand) { return cand_args(v, n_cand, region_dev(-1.0, nullptr, 0, -1)); }
-
-__device__ __forceinline__ uint32_t simkey_of(float best)
-{
-    const uint32_t sk = float_desc_key(best);
-    return sk == 0xffffffffu ? 0xfffffffeu : sk;     // keep the all-ones pattern for "no candidate"
-}
 
 __device__ __forceinline__ uint32_t cand_val(const CandArgs &, int c) { return (uint32_t)c; }
 __device__ __forceinline__ uint32_t cand_rank(const CandArgs &a, int c) { return a.name_rank[c]; }
@@ -208,27 +132,11 @@ __device__ __forceinline__ uint32_t cand_simkey(const CandArgs &a, int c, int, c
     return simkey_of(a.best_sim(e, m, sims));
 }
 
-__device__ __forceinline__ uint32_t cand_val(const RegionCandArgs &a, int i) { return a.cidx ? (i < a.n_cand ? a.cidx[i] : 0u) : (uint32_t)i; }
 __device__ __forceinline__ uint32_t cand_rank(const RegionCandArgs &a, int i) { return a.name_rank[cand_val(a, i)]; }
 __device__ __forceinline__ uint32_t cand_simkey(const RegionCandArgs &a, int i, int q, const float *__restrict__ sims)
 {
-    if (i >= a.n_cand) return 0xffffffffu;
-    const int c = (int)cand_val(a, i);
-    const int e = a.entry(c);
-    const int m = a.cnt[e];
-    if (a.mask) {                  // the visibility pass made the test (empty voxels see nothing there)
-        if (!((a.mask[(int64_t)(q >> 5) * a.mask_stride + c] >> (q & 31)) & 1u)) return 0xffffffffu;
-    } else {
-        if (m <= 0) return 0xffffffffu;
-        int r, cc, h;
-        a.position(c, r, cc, h);
-        if (!region_sees(a.regions[q], r, cc, h)) return 0xffffffffu;
-    }
-    if (!a.rowoff) return simkey_of(a.best_sim(e, m, sims));
-    float best = -INFINITY;        // gathered rows of entry i are consecutive
-    const int base = a.rowoff[i], nr = a.exact ? m : 1;
-    for (int k = 0; k < nr; ++k) best = fmaxf(best, sims[base + k]);
-    return simkey_of(best);
+    float best;
+    return cand_score(a, i, q, sims, best) ? simkey_of(best) : 0xffffffffu;
 }
 
 // full rank key: similarity descending, ties in HDF5 name order
@@ -886,8 +794,9 @@ __global__ __launch_bounds__(TPB) void k_fill_no_result(int64_t n, int32_t *__re
     out_sim[i] = -INFINITY;
 }
 
-bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, const bsc_region *regions,
-                                 int32_t *out_pos, float *out_sim, int32_t *out_count)
+// The front half of bsc_localize_regions, shared with bsc_score_map (score_map.hip): both calls run the identical scan, on the same
+// rows with the same kernel choice, so their scores agree bit for bit.
+bsc_status region_scan(bsc_ctx *x, const float *q_dev, int32_t nq, const bsc_region *regions, RegionScan *out)
 {
     hipStream_t s = x->stream;
     const int D = x->c.token_dim;
@@ -904,8 +813,8 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
     // the regions as the kernels read them; a query with neither sphere nor band sees every voxel
     bool any_open = false, all_open = true;
     for (int qi = 0; qi < nq; ++qi) {
-        const bsc_region &g = regions[qi];
-        w->regions_pin[qi] = region_dev(g.radius, g.curr, g.floor_lo, g.floor_hi);
+        w->regions_pin[qi] = regions ? region_dev(regions[qi].radius, regions[qi].curr, regions[qi].floor_lo, regions[qi].floor_hi)
+                                     : region_dev(-1.0, nullptr, 0, -1);
         if (region_open(w->regions_pin[qi])) any_open = true;
         else all_open = false;
     }
@@ -945,15 +854,11 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
             pruned = always || (double)n_vis_rows < share * (double)n_rows;
         }
     }
-    if (pruned && n_vis == 0) {            // no query sees anything
-        hipLaunchKernelGGL(k_fill_no_result, dim3((unsigned)(((int64_t)nq * K + TPB - 1) / TPB)), block, 0, s, (int64_t)nq * K,
-                           x->l_out_pos, x->l_out_sim);
-        BSC_HIP(hipGetLastError());
-        BSC_HIP(hipStreamSynchronize(s));
-        for (int64_t i = 0; i < (int64_t)nq * K; ++i) { out_pos[3 * i] = out_pos[3 * i + 1] = out_pos[3 * i + 2] = -1; out_sim[i] = -INFINITY; }
-        record_counts(x, nq, K, out_pos, out_count);      // all zero
-        return BSC_OK;
-    }
+    out->n_voxels = n_cand;
+    out->all_open = all_open;
+    out->nothing = pruned && n_vis == 0;   // no query sees anything
+    out->sstride = 0;
+    if (out->nothing) return BSC_OK;
     const float *scan_rows = rows;
     int64_t scan_n = n_rows;
     float2 **rs = &x->l_rscale;
@@ -975,17 +880,35 @@ bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int
         rs = &w->rscale; rs_cap = &w->rscale_cap; rs_dirty = &scratch_dirty;
     }
     stat_begin(x, 1);
-    const int64_t sstride = sims_row_stride(scan_n);
+    out->sstride = sims_row_stride(scan_n);
     int passes = 0;
     BSC_TRY(cosine_scan(x, scan_rows, scan_n, nq, rs, rs_cap, rs_dirty, &passes));
     stat_end(x, 1, (double)scan_n * D * 4.0 * passes + (double)nq * scan_n * 4.0);
-    if (all_open)                          // no region anywhere: bsc_localize's own selection (its dense fast filter included)
-        return select_and_copy_out(x, cand_args_open(v, n_cand), nq, K, sstride, /*strict*/ 1, out_pos, out_sim, out_count);
-    RegionCandArgs ca;
+    RegionCandArgs &ca = out->ca;
     (VoxelView &)ca = v;
     ca.n_cand = pruned ? (int)n_vis : n_cand;
     ca.regions = w->regions;
     ca.mask = pass ? w->mask : nullptr; ca.mask_stride = mask_stride;
     ca.cidx = pruned ? w->cidx : nullptr; ca.rowoff = pruned ? w->rowoff : nullptr;
-    return select_and_copy_out(x, ca, nq, K, sstride, /*strict*/ 0, out_pos, out_sim, out_count);
+    return BSC_OK;
+}
+
+bsc_status localize_regions_impl(bsc_ctx *x, const float *q_dev, int32_t nq, int32_t K, const bsc_region *regions,
+                                 int32_t *out_pos, float *out_sim, int32_t *out_count)
+{
+    hipStream_t s = x->stream;
+    RegionScan rg;
+    BSC_TRY(region_scan(x, q_dev, nq, regions, &rg));
+    if (rg.nothing) {
+        hipLaunchKernelGGL(k_fill_no_result, dim3((unsigned)(((int64_t)nq * K + TPB - 1) / TPB)), dim3(TPB), 0, s, (int64_t)nq * K,
+                           x->l_out_pos, x->l_out_sim);
+        BSC_HIP(hipGetLastError());
+        BSC_HIP(hipStreamSynchronize(s));
+        for (int64_t i = 0; i < (int64_t)nq * K; ++i) { out_pos[3 * i] = out_pos[3 * i + 1] = out_pos[3 * i + 2] = -1; out_sim[i] = -INFINITY; }
+        record_counts(x, nq, K, out_pos, out_count);      // all zero
+        return BSC_OK;
+    }
+    if (rg.all_open)                       // no region anywhere: bsc_localize's own selection (its dense fast filter included)
+        return select_and_copy_out(x, cand_args_open(rg.ca, rg.n_voxels), nq, K, rg.sstride, /*strict*/ 1, out_pos, out_sim, out_count);
+    return select_and_copy_out(x, rg.ca, nq, K, rg.sstride, /*strict*/ 0, out_pos, out_sim, out_count);
 }

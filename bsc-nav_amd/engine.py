@@ -64,6 +64,14 @@ def region_array(Q, radius=None, curr=None, floor=None):
     return out
 
 
+def score_map_regions(Q, radius=None, curr=None, floor=None):
+    """The regions argument of VoxelEngine.score_map (needs no context): None — a NULL pointer, no region for any query — when
+    radius, curr and floor are all None, otherwise region_array's (Q,) array."""
+    if radius is None and curr is None and floor is None:
+        return None
+    return region_array(Q, radius, curr, floor)
+
+
 def pad_cluster_batch(pos, sim, counts=None):
     """The (pos (Q,K,3) int32, sim (Q,K) float32, counts (Q,) int32) arrays of VoxelEngine.cluster_centers_batch from its
     arguments (needs no context).  pos / sim are either arrays of those shapes, with counts (None: K points each, otherwise
@@ -378,6 +386,24 @@ class VoxelEngine:
         _lib.check(self.lib.bsc_localize_regions(self.h, _dp(q), Q, K, _hp(regions), _hp(pos), _hp(sim), _hp(cnt)))
         self._last_localize = (Q, K, cnt.copy())
         return pos, sim, cnt
+
+    def score_map(self, q, radius=None, curr=None, floor=None, heights=True):
+        """The best score per top-down cell for every query (bsc_score_map): q (Q,D) or (D) f32 CUDA; radius / curr / floor
+        as in localize_regions (all three None: no region for any query)
+        -> (score (Q,gs,gs) f32 CUDA, height (Q,gs,gs) i32 CUDA or None when heights is False).
+        score[i,r,c] is the largest score among the voxels of column (r,c) that localize_regions would rank for query i, with
+        the bits it has there (-inf: none); height[i,r,c] the stored h of the voxel that has it, the smallest h among equals
+        (-1: none).  The resident results of the last localize call are untouched."""
+        q = q.reshape(-1, self.cfg.token_dim).contiguous()
+        assert q.is_cuda and q.dtype == torch.float32
+        Q, gs = q.shape[0], self.cfg.grid_size
+        regions = score_map_regions(Q, radius, curr, floor)
+        score = torch.empty((Q, gs, gs), dtype=torch.float32, device=q.device)
+        height = torch.empty((Q, gs, gs), dtype=torch.int32, device=q.device) if heights else None
+        self._enter(q, score, height)
+        _lib.check(self.lib.bsc_score_map(self.h, _dp(q), Q, _hp(regions), _dp(score), _dp(height)))
+        self._leave()
+        return score, height
 
     def cluster_centers(self, pos=None, sim=None, K=None, query_index=0, eps=10.0, min_samples=5):
         """BSCAgent.weighted_cluster_centers on the GPU -> (centers (n,3) f64, labels (K,) int, sizes list).

@@ -409,6 +409,21 @@ class VoxelTokenMemory:
         self._log(f"finish localizing {Q} prompts, time:{time.time() - t1}")
         return out
 
+    def voxel_score_map(self, prompts, region_radius=np.inf, curr_grid=None, floors=None):
+        """The field voxel_localized_batch ranks from: for every prompt the best score per top-down cell (r, c) and the height
+        of the voxel that has it (VoxelEngine.score_map) — a value map for a planner, a heat map over cv_map.  prompts,
+        region_radius, curr_grid and floors follow voxel_localized_batch, the loaded single floor (args.load_single_floor)
+        included -> (score (Q,gs,gs) f32, height (Q,gs,gs) i32) torch tensors on the device; -inf / -1 where a prompt's
+        region holds no voxel of the column."""
+        if isinstance(prompts, torch.Tensor) and prompts.dim() == 2:
+            q = prompts.to(self.device, torch.float32).contiguous()
+        else:
+            q = torch.cat([self._query_embedding(p) for p in prompts], 0)
+        Q = q.shape[0]
+        if floors is None and getattr(self.args, "load_single_floor", False) and hasattr(self, "floor_min_height"):
+            floors = [(self.floor_min_height, self.floor_max_height)] * Q
+        return self.engine.score_map(q, radius=region_radius, curr=curr_grid, floor=floors)
+
     def weighted_cluster_centers(self, top_k_positions, top_k_similarity, eps=10, min_samples=5):
         """GESObjectNavRobot.weighted_cluster_centers (BSCAgent.py:479-497) on the GPU: DBSCAN over the top-K voxel
         positions + similarity-weighted centres -> (cluster_centers (n,3) f64, labels (K,), cluster_sizes)."""

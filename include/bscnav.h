@@ -212,6 +212,27 @@ bsc_status bsc_localize_regions(bsc_ctx *ctx, const float *q_dev, int32_t n_quer
                                 const bsc_region *regions_host /* (Q) */, int32_t *out_pos_host, float *out_sim_host,
                                 int32_t *out_count_host);
 
+/* The score map of a batch of queries: what voxel_localized computes before it keeps K (memory_2.py:623-671), as a field over the
+ * top-down grid instead of a ranked list — a value map for a frontier / value-map planner to add to bsc_frontier_clusters' gains, a
+ * heat map to lay over cv_map, something to threshold.  For query i and cell (r, c), 0 <= r, c < grid_size, let S be the candidates
+ * bsc_localize_regions would rank for query i (a stored voxel with tokens that region i sees: the sphere and floor-band rules of
+ * :624-640, exactly as described at bsc_region; the grid_0_0_0 group counts at (0, 0, 0), where bsc_localize reports it) whose
+ * position has row r and column c.
+ *   score_dev[i, r, c]   the largest score in S, a voxel's score being the f32 maximum of its tokens' cosines (:655-661) with the
+ *                        very bits bsc_localize_regions reports for it under the same settings; -inf when S is empty.
+ *   height_dev[i, r, c]  the stored h (third coordinate of grid_rgb_pos, after the -min_h shift) of the voxel that has that score,
+ *                        the smallest such h when several tie; -1 when S is empty.  May be NULL.
+ * Both are caller-owned device buffers of (Q, grid_size, grid_size) elements, f32 / i32, indexed in 64 bits.  regions_host NULL:
+ * no region for any query.  The result does not depend on voxel id order or timing and is bit-reproducible.  The call returns
+ * after its work on the context's stream has completed; the resident results of the last bsc_localize / bsc_localize_regions call
+ * are untouched.  All three modes; an empty memory gives BSC_OK and -inf / -1 everywhere.  The keys the kernels reduce are scratch
+ * of the context, bounded by working through the queries in chunks: BSC_SCORE_MAP_CHUNK_MB (read per call, default 256).
+ * BSC_E_INVALID, nothing written: a NULL context, q_dev or score_dev, n_queries outside 1..1024, with regions given a NaN radius
+ * or reserved != 0. */
+bsc_status bsc_score_map(bsc_ctx *ctx, const float *q_dev, int32_t n_queries,
+                         const bsc_region *regions_host /* (Q) or NULL: no region for any query */,
+                         float *score_dev /* (Q, gs, gs) f32 */, int32_t *height_dev /* (Q, gs, gs) i32, may be NULL */);
+
 /* GESObjectNavRobot.weighted_cluster_centers (BSCAgent.py:479-497), the consumer of voxel_localized's output:
  * DBSCAN(eps, min_samples) over K top-ranked positions (scikit-learn semantics), similarity-weighted centres,
  * clusters ordered by mean similarity (stable, descending).  pos_host (K,3) / sim_host (K) NULL = cluster the first K
