@@ -20,7 +20,7 @@ enum {
     BSC_STAT_COSINE = 1,   // cosine scan of bsc_localize / bsc_localize_regions (bytes: the rows actually streamed)
     BSC_STAT_POINTS = 2,   // k_points
     BSC_STAT_PAIRS = 3,    // k_keys_pairs + tile scan + k_pair_compact
-    BSC_STAT_ORDER = 4,    // new-voxel ids, k_runs, run sort, scan, k_expand, segment order (everything the rgb chain needs)
+    BSC_STAT_ORDER = 4,    // new-voxel ids, k_run_keys, run sort, scan, k_expand, segment order (everything the rgb chain needs)
     BSC_STAT_PAIRSORT = 5, // pair sort + segment heads
     BSC_STAT_INGEST = 6,   // main-stream work of one bsc_ingest call, first to last kernel
     BSC_STAT_CHAIN = 7,    // k_chain + k_hwin (side stream)
@@ -62,6 +62,25 @@ struct RadixWs {
     uint32_t epoch;            // host counter: one value per (sort, pass)
 };
 
+// the scratch a call shares with its rgb chain, double-buffered: the chain of call n reads set n & 1 on the side stream while
+// call n + 1 fills the other
+struct IngestSet {
+    PointRec *p_rec;                // read by the rgb chain on the side stream
+    uint32_t *skey_b;               // sorted run keys
+    uint32_t *sval_b;               // point order: j of the k-th point, voxel by voxel — written only where the quad chain reads it
+                                    // (short segments, the first points of new voxels: k_expand_short)
+    // the point order by RUNS (read by k_chain_long): position k belongs to the run whose start is the last set bit at or below k
+    u64 *run_bits;                  // bit k: a run starts at position k
+    uint32_t *ck_run, *ck_start;    // per 64 positions: the sorted run that covers position 64 w, and where it starts
+    uint32_t *run_val;              // sorted run values (first record of the run)
+    int4 *seg_info;                 // per voxel segment: {first k, end k, voxel id, rank in the length-class order}
+    int32_t *seg_last;
+    int64_t *bscal;                 // per-set scalars: [0] voxel segments of the batch, [1] max_id before the batch
+    bool rec8;                      // record format of the call in this set (its chain is launched later)
+    hipEvent_t ev_ready, ev_done;   // side: the set's point order is complete; its chain is done with the set
+    bool ev_done_valid;
+};
+
 struct SurpriseWs;   // surprise.hip: scratch of bsc_flush_surprise, allocated on its first call
 struct RegionWs;     // localize.hip: scratch of bsc_localize_regions, allocated on its first call
 struct ClusterWs;    // cluster.hip: inputs, result block and pinned staging of bsc_cluster_centers(_batch), grown on demand
@@ -90,7 +109,6 @@ struct bsc_ctx {
     // depth range (min_depth, max_depth) spans fewer than 2^28 values (BSC_REC12=1 keeps the 12-byte {alpha, rgb} records)
     bool rec8_ok;
     uint32_t rec8_zbase;       // bits of the largest float <= min_depth
-    bool rec8_s[2];            // record format of the call in scratch set k (its chain is launched later)
     uint8_t *pat_x, *pat_y;   // (W), (H): patch column / row of a pixel column / row, 255 = outside the patch grid
     double *exp_tab;          // 64 x (hi, lo) of 2^(j/64): the table of bsc_exp (geometry_dev.h)
     // patch-aligned pair tiles (dense.hip): pixel rectangle {x0, width, y0, pixels} of every patch and the start of its
@@ -131,7 +149,6 @@ struct bsc_ctx {
     // ---- per-batch scratch (max_points) ----
     int32_t *p_cell;
     uint32_t *p_patf;
-    PointRec *p_rec_s[2];    // double-buffered: read by the rgb chain on the side stream
     float *p_r2f;
     // Points are ordered per voxel through their RUNS (maximal stretches of consecutive points in one cell; a 10 cm
     // voxel a few metres away covers ~16 pixels of an image row): the runs are sorted by voxel id (stable radix sort
@@ -144,32 +161,23 @@ struct bsc_ctx {
     uint32_t *stage_cell, *stage_pos;   // k_points: the runs of every block of points (cell, first position), slice b * GB
     int group_rpw;                      // rounds of 64 points per wavefront in k_points: 4 (1024-point blocks) or 8 (2048; BSC_GROUP_RPW)
     uint32_t *skey_a, *sval_a;          // run sort input: key = voxel id | (length - 1) << id bits, value = first point
-    uint32_t *skey_b_s[2];              // sorted run keys
     uint32_t *run_val_b;                // sorted run values
     int64_t *run_scan;                  // per 1024-run block: sum, then exclusive prefix, of (length | segment head << 32)
     int32_t *seg_k0, *seg_vid;          // voxel segments of the point order: first position, voxel id
-    uint32_t *sval_b_s[2];              // point order: j of the k-th point, voxel by voxel — written only where the quad chain reads it
-                                        // (short segments, the first points of new voxels: k_expand_short)
-    // the point order by RUNS (read by k_chain_long): position k belongs to the run whose start is the last set bit at or below k
-    u64 *run_bits_s[2];                 // bit k: a run starts at position k
-    uint32_t *ck_run_s[2], *ck_start_s[2];   // per 64 positions: the sorted run that covers position 64 w, and where it starts
-    uint32_t *run_val_s[2];             // sorted run values (first record of the run), per scratch set
-    int4 *seg_info_s[2];                // per voxel segment: {first k, end k, voxel id, rank in the length-class order}
     u64 *f_keys_a, *f_keys_b;  // flush-private sort buffers (iter_size)
     int32_t *pass_list;
-    int32_t *seg_last_s[2];
-    int64_t *bscal_s[2];       // per-set scalars: [0] voxel segments of the batch, [1] max_id before the batch
+    IngestSet set[2];
     int cur_set;
     hipStream_t side;          // rgb chain + top-down map run here, overlapped with the dense reduce / next encoder
     hipStream_t side2;         // the one-wavefront segments of the long chain, beside the hot tiles on `side`
     hipEvent_t ev_chain0, ev_mid;
-    hipEvent_t ev_ready[2], ev_done[2];
-    bool ev_done_valid[2];
-    bool chain_pending;        // the last call's rgb chain / top-down map kernels are still to be launched (deferred)
-    int chain_set;
+    struct {
+        bool pending;          // the last call's rgb chain / top-down map kernels are still to be launched (deferred)
+        int set;
+        int64_t order_base;
+        int64_t points;        // points of the batch whose chain is pending
+    } chain;
     int last_chain_set;        // scratch set of the most recently launched chain (-1: none since the last reset)
-    int64_t chain_order_base;
-    int64_t chain_points;      // points of the batch whose chain is pending
     u64 *pair_key_a, *pair_key_b;   // dense: voxel id << cb | frame << pb | patch
     u64 *pstage_key;                // per-tile staging of the LDS-aggregated pairs
     uint32_t *pstage_cnt;
@@ -228,9 +236,9 @@ struct bsc_ctx {
     void *prim_tmp_side;       // second rocPRIM workspace: the order pipeline sorts on the side stream beside the pair sort
     RadixWs rx_main, rx_side;  // in-tree radix sort: the pair sort (main stream) and the run sort (side stream) may run at the same time
     bool radix_intree;         // BSC_SORT_ROCPRIM=1: both sorts through rocPRIM as until round 5
-    bool order_on_side;        // per-voxel point order (k_runs .. k_seg_order) on the side stream (BSC_ORDER_MAIN=1 keeps it on the main stream)
-    hipEvent_t ev_ids, ev_runs;   // voxel ids assigned; side: k_runs has read the call's cells / block offsets
-    hipEvent_t ev_tot;            // main: k_totals done (the call's run / new-voxel counts exist)
+    bool order_on_side;        // per-voxel point order (k_run_keys .. k_expand_short) on the side stream (BSC_ORDER_MAIN=1 keeps it on the main stream)
+    hipEvent_t ev_ids, ev_runs;   // voxel ids assigned; side: k_run_keys / k_pass_list have read the call's cells / block offsets
+    hipEvent_t ev_tot;            // main: k_block_totals done (the call's run / new-voxel counts exist)
     hipEvent_t ev_psort;          // main: the pair sort of the last call is done (the rgb chain starts behind it, launch_pending_chain)
     bool ev_psort_valid;
     hipStream_t copy;             // early readback of those counts while the main stream goes on with the pair tiles
@@ -296,24 +304,35 @@ __device__ __forceinline__ void block_scan2(int a, int b, int &ea, int &eb, int 
     eb = bb + ib - b;
 }
 
-// ---- primitives (prims.hip; rocPRIM device-wide sort and scans) ----
+// ---- primitives (prims.hip: rocPRIM device-wide sort and scans; radix.hip: the in-tree sort) ----
+// where a primitive runs: its stream and the workspaces that belong to that stream
+struct PrimLane { hipStream_t stream; void *tmp; size_t tmp_bytes; RadixWs *rx; };
+static inline PrimLane lane_main(bsc_ctx *x) { return {x->stream, x->prim_tmp, x->prim_tmp_bytes, &x->rx_main}; }
+static inline PrimLane lane_side(bsc_ctx *x) { return {x->side, x->prim_tmp_side, x->prim_tmp_bytes, &x->rx_side}; }
 size_t prim_workspace_bytes(size_t max_items);
-bsc_status prim_sort_keys(bsc_ctx *x, const u64 *in, u64 *out, size_t n, int begin_bit, int end_bit);
-bsc_status prim_sort_pairs(bsc_ctx *x, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, size_t n,
+bsc_status prim_sort_keys(const PrimLane &l, const u64 *in, u64 *out, size_t n, int begin_bit, int end_bit);
+bsc_status prim_sort_pairs(const PrimLane &l, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, size_t n,
                            int begin_bit, int end_bit);
-bsc_status prim_sort_pairs_onesweep(bsc_ctx *x, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, size_t n,
+bsc_status prim_sort_pairs_onesweep(const PrimLane &l, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, size_t n,
                                     int begin_bit, int end_bit);
-bsc_status prim_sort_pairs_u32(bsc_ctx *x, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
+bsc_status prim_sort_pairs_u32(const PrimLane &l, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
                                size_t n, int begin_bit, int end_bit);
-bsc_status prim_sort_pairs_u32_onesweep(bsc_ctx *x, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
+bsc_status prim_sort_pairs_u32_onesweep(const PrimLane &l, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
                                         size_t n, int begin_bit, int end_bit);
 // in-tree onesweep radix sort of (u32 key, u32 value) pairs on the key bits [b0, b1): stable, input preserved (radix.hip)
 bsc_status radix_ws_create(BscMem *m, RadixWs *ws, size_t max_items);      // the buffers are the ledger's
-bsc_status radix_sort_pairs_u32(bsc_ctx *x, RadixWs *ws, hipStream_t st, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
-                                uint32_t *vout, size_t n, int b0, int b1);
-bsc_status prim_exclusive_sum_i64(bsc_ctx *x, const int64_t *in, int64_t *out, size_t n);
-bsc_status prim_exclusive_sum_i32(bsc_ctx *x, const int32_t *in, int32_t *out, size_t n);
-bsc_status prim_inclusive_max_i32(bsc_ctx *x, const int32_t *in, int32_t *out, size_t n);
+bsc_status radix_sort_pairs_u32(const PrimLane &l, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n,
+                                int b0, int b1);
+// the (u32, u32) pair sort of the pipeline: in-tree radix, or rocPRIM under BSC_SORT_ROCPRIM=1 (onesweep: its one-sweep form)
+static inline bsc_status sort_pairs_u32(const bsc_ctx *x, const PrimLane &l, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
+                                        uint32_t *vout, size_t n, int b0, int b1, bool onesweep = false)
+{
+    if (x->radix_intree) return radix_sort_pairs_u32(l, kin, kout, vin, vout, n, b0, b1);
+    return onesweep ? prim_sort_pairs_u32_onesweep(l, kin, kout, vin, vout, n, b0, b1) : prim_sort_pairs_u32(l, kin, kout, vin, vout, n, b0, b1);
+}
+bsc_status prim_exclusive_sum_i64(const PrimLane &l, const int64_t *in, int64_t *out, size_t n);
+bsc_status prim_exclusive_sum_i32(const PrimLane &l, const int32_t *in, int32_t *out, size_t n);
+bsc_status prim_inclusive_max_i32(const PrimLane &l, const int32_t *in, int32_t *out, size_t n);
 
 // ---- kernels launchers ----
 bsc_status launch_geometry_debug(bsc_ctx *x, const float *depth, const int32_t *idx, int64_t P, uint8_t *flags,

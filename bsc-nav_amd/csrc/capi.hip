@@ -64,10 +64,10 @@ static void fill(bsc_ctx *x, T *p, int64_t n, T v)
 static bsc_status reset_state(bsc_ctx *x)
 {
     hipStream_t s = x->stream;
-    x->chain_pending = false;                  // the state it would update is being cleared
+    x->chain.pending = false;                  // the state it would update is being cleared
     x->last_chain_set = -1;
     if (x->side) BSC_HIP(hipStreamSynchronize(x->side));
-    x->ev_done_valid[0] = x->ev_done_valid[1] = false;
+    x->set[0].ev_done_valid = x->set[1].ev_done_valid = false;
     x->ev_runs_valid = false;
     x->last_order_set = -1;
     const int64_t gs2 = (int64_t)x->c.grid_size * x->c.grid_size;
@@ -268,11 +268,15 @@ static bsc_status ctx_build(bsc_ctx *x)
     ALLOC(x->hb_cnt, x->nblk_cap); ALLOC(x->hb_off, x->nblk_cap);
     ALLOC(x->pass_list, np);
     for (int k = 0; k < 2; ++k) {
-        ALLOC(x->p_rec_s[k], np); ALLOC(x->skey_b_s[k], np); ALLOC(x->sval_b_s[k], np);
-        ALLOC(x->run_bits_s[k], np / 64 + 2); ALLOC(x->ck_run_s[k], np / 64 + 2); ALLOC(x->ck_start_s[k], np / 64 + 2); ALLOC(x->run_val_s[k], np);
-        ALLOC(x->seg_info_s[k], (np < vcap ? np : vcap) + 1); ALLOC(x->seg_last_s[k], (np < vcap ? np : vcap) + 1); ALLOC(x->bscal_s[k], 8);
-        BSC_HIP(hipEventCreateWithFlags(&x->ev_ready[k], hipEventDisableTiming));
-        BSC_HIP(hipEventCreateWithFlags(&x->ev_done[k], hipEventDisableTiming));
+        IngestSet &S = x->set[k];
+        // (the ledger labels these buffers have always had)
+#define ALLOC_SET(member, count) BSC_TRY(mem_alloc(x->mem, (void **)&S.member, sizeof(*S.member) * (size_t)(count), "x->" #member "_s[k]"))
+        ALLOC_SET(p_rec, np); ALLOC_SET(skey_b, np); ALLOC_SET(sval_b, np);
+        ALLOC_SET(run_bits, np / 64 + 2); ALLOC_SET(ck_run, np / 64 + 2); ALLOC_SET(ck_start, np / 64 + 2); ALLOC_SET(run_val, np);
+        ALLOC_SET(seg_info, (np < vcap ? np : vcap) + 1); ALLOC_SET(seg_last, (np < vcap ? np : vcap) + 1); ALLOC_SET(bscal, 8);
+#undef ALLOC_SET
+        BSC_HIP(hipEventCreateWithFlags(&S.ev_ready, hipEventDisableTiming));
+        BSC_HIP(hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming));
     }
     {
         int lo = 0, hi = 0;   // rgb chain: latency-bound, give it the highest priority the device offers
@@ -382,8 +386,8 @@ extern "C" void bsc_destroy(bsc_ctx *x)
     if (x->ev_psort) hipEventDestroy(x->ev_psort);
     if (x->copy) hipStreamDestroy(x->copy);
     for (int k = 0; k < 2; ++k) {
-        if (x->ev_ready[k]) hipEventDestroy(x->ev_ready[k]);
-        if (x->ev_done[k]) hipEventDestroy(x->ev_done[k]);
+        if (x->set[k].ev_ready) hipEventDestroy(x->set[k].ev_ready);
+        if (x->set[k].ev_done) hipEventDestroy(x->set[k].ev_done);
     }
     for (int w = 0; w < BSC_STAT_SLOTS; ++w)
         for (int i = 0; i < 2 * BSC_EV_RING; ++i)
@@ -415,7 +419,7 @@ extern "C" bsc_status bsc_stream_wait_chain(bsc_ctx *x, void *hip_stream)
     BSC_HIP(hipSetDevice(x->device));
     // the most recently LAUNCHED chain (a deferred one that has not been launched yet is not waited for)
     const int last = x->last_chain_set;
-    if (last >= 0 && x->ev_done_valid[last]) BSC_HIP(hipStreamWaitEvent((hipStream_t)hip_stream, x->ev_done[last], 0));
+    if (last >= 0 && x->set[last].ev_done_valid) BSC_HIP(hipStreamWaitEvent((hipStream_t)hip_stream, x->set[last].ev_done, 0));
     return BSC_OK;
 }
 
@@ -608,7 +612,7 @@ extern "C" bsc_status bsc_sort_pairs_u32(bsc_ctx *x, const uint32_t *keys_dev, c
     if (!x || n < 0 || (n > 0 && (!keys_dev || !vals_dev || !keys_out_dev || !vals_out_dev)) || begin_bit < 0 || end_bit > 32 || begin_bit > end_bit)
         return BSC_E_INVALID;
     BSC_HIP(hipSetDevice(x->device));
-    return radix_sort_pairs_u32(x, &x->rx_main, x->stream, keys_dev, keys_out_dev, vals_dev, vals_out_dev, (size_t)n, begin_bit, end_bit);
+    return radix_sort_pairs_u32(lane_main(x), keys_dev, keys_out_dev, vals_dev, vals_out_dev, (size_t)n, begin_bit, end_bit);
 }
 
 // ---- exports ---------------------------------------------------------------------------------------

@@ -423,9 +423,9 @@ static bsc_status compact_heads(bsc_ctx *x, const K *keys, int64_t n, int shift,
 {
     const int64_t nb = (n + HB - 1) / HB;
     if (nb > x->nblk_cap) { bsc_set_error("compact_heads: block table too small"); return BSC_E_CAPACITY; }
-    // own count / offset tables: blk_cnt / blk_off hold the run counts of the batch until k_runs has consumed them
+    // own count / offset tables: blk_cnt / blk_off hold the run counts of the batch until k_run_keys has consumed them
     hipLaunchKernelGGL((k_head_count<K>), dim3((unsigned)nb), dim3(TPB), 0, x->stream, keys, n, shift, invalid, x->hb_cnt);
-    BSC_TRY(prim_exclusive_sum_i32(x, x->hb_cnt, x->hb_off, (size_t)nb));
+    BSC_TRY(prim_exclusive_sum_i32(lane_main(x), x->hb_cnt, x->hb_off, (size_t)nb));
     hipLaunchKernelGGL((k_head_write<K>), dim3((unsigned)nb), dim3(TPB), 0, x->stream, keys, n, shift, invalid, x->hb_off,
                        out, count_dev);
     BSC_HIP(hipGetLastError());
@@ -1066,7 +1066,7 @@ bsc_status launch_keys_pairs(bsc_ctx *x, int64_t P, int n_frames, bool all_pixel
         uint32_t *pair_idx = (uint32_t *)x->pair_key_b;
         hipLaunchKernelGGL(k_patch_pairs, pgrid, block, 0, x->stream, W, N, x->c.patch_grid, tiles, x->pt_rect, x->pt_off,
                            make_cell_code32(x), x->p_cell, x->pstage_key, x->pstage_cnt, x->tile_cnt);
-        BSC_TRY(prim_exclusive_sum_i32(x, x->tile_cnt, x->tile_off, (size_t)tiles));
+        BSC_TRY(prim_exclusive_sum_i32(lane_main(x), x->tile_cnt, x->tile_off, (size_t)tiles));
         hipLaunchKernelGGL(k_patch_compact, grid, block, 0, x->stream, tiles, g2, N, x->pt_off, x->tile_cnt, x->tile_off,
                            x->pstage_key, x->pstage_cnt, x->pair_key_a, x->pair_cnt_a, pair_idx, x->pair_cap, x->dscal);
         BSC_HIP(hipGetLastError());
@@ -1079,7 +1079,7 @@ bsc_status launch_keys_pairs(bsc_ctx *x, int64_t P, int n_frames, bool all_pixel
     const dim3 grid((unsigned)tiles), block(TPB);
     hipLaunchKernelGGL(k_keys_pairs, grid, block, 0, x->stream, P, all_pixels ? 1 : 0, H, W, tx_n, ty_n, make_cell_code(x, cb),
                        x->p_cell, p_patf, x->pat_x, x->pat_y, x->c.patch_grid, x->pstage_key, x->pstage_cnt, x->tile_cnt, pb, cb);
-    BSC_TRY(prim_exclusive_sum_i32(x, x->tile_cnt, x->tile_off, (size_t)tiles));
+    BSC_TRY(prim_exclusive_sum_i32(lane_main(x), x->tile_cnt, x->tile_off, (size_t)tiles));
     hipLaunchKernelGGL(k_pair_compact, grid, block, 0, x->stream, tiles, x->tile_cnt, x->tile_off, x->pstage_key,
                        x->pstage_cnt, x->pair_key_a, x->pair_cnt_a, x->pair_cap, x->dscal);
     BSC_HIP(hipGetLastError());
@@ -1102,10 +1102,7 @@ bsc_status dense_reduce_batch(bsc_ctx *x, const void *tokens, int token_dtype, i
         const CellCode cc = make_cell_code32(x);
         uint32_t *pair_idx = (uint32_t *)x->pair_key_b, *idx_sorted = pair_idx + x->pair_cap;
         stat_begin(x, BSC_STAT_PAIRSORT);
-        if (x->radix_intree)
-            BSC_TRY(radix_sort_pairs_u32(x, &x->rx_main, s, x->pair_cnt_a, x->pair_cnt_b, pair_idx, idx_sorted, (size_t)n_pairs, 0, cell_code_bits(cc)));
-        else
-            BSC_TRY(prim_sort_pairs_u32_onesweep(x, x->pair_cnt_a, x->pair_cnt_b, pair_idx, idx_sorted, (size_t)n_pairs, 0, cell_code_bits(cc)));
+        BSC_TRY(sort_pairs_u32(x, lane_main(x), x->pair_cnt_a, x->pair_cnt_b, pair_idx, idx_sorted, (size_t)n_pairs, 0, cell_code_bits(cc), true));
         BSC_TRY(compact_heads_u32(x, x->pair_cnt_b, n_pairs, x->pseg_start, x->dscal + DS_B_NPSEG));
         stat_end(x, BSC_STAT_PAIRSORT, 0.0);
         BSC_HIP(hipEventRecord(x->ev_psort, s));        // the rgb chain of this call starts behind the pair sort (launch_pending_chain)
@@ -1191,7 +1188,7 @@ bsc_status dense_reduce_batch(bsc_ctx *x, const void *tokens, int token_dtype, i
     }
     const int pb = code_patch_bits(x), cb = code_bits(x, n_frames);
     stat_begin(x, BSC_STAT_PAIRSORT);
-    BSC_TRY(prim_sort_pairs_onesweep(x, x->pair_key_a, x->pair_key_b, x->pair_cnt_a, x->pair_cnt_b, (size_t)n_pairs, 0,
+    BSC_TRY(prim_sort_pairs_onesweep(lane_main(x), x->pair_key_a, x->pair_key_b, x->pair_cnt_a, x->pair_cnt_b, (size_t)n_pairs, 0,
                                      cb + cell_code_bits(make_cell_code(x, cb))));
     // voxel segments of the sorted list, already in Morton order of the cells
     BSC_TRY(compact_heads_u64(x, x->pair_key_b, n_pairs, cb, x->pseg_start, x->dscal + DS_B_NPSEG));

@@ -174,14 +174,14 @@ bsc_status flush_cache(bsc_ctx *x, bsc_draw_fn draw, void *user)
     BSC_TRY(reserve_pool_rows(x, n));
     hipLaunchKernelGGL(k_flush_keys, grid, block, 0, s, n, x->cache_pos, x->occ, x->c.grid_size, x->nh,
                        x->c.voxel_capacity, x->f_keys_a);
-    BSC_TRY(prim_sort_keys(x, x->f_keys_a, x->f_keys_b, (size_t)n, 0, 20 + ebits));
+    BSC_TRY(prim_sort_keys(lane_main(x), x->f_keys_a, x->f_keys_b, (size_t)n, 0, 20 + ebits));
     hipLaunchKernelGGL(k_flush_heads, grid, block, 0, s, n, x->f_keys_b, x->f_hit /*tmp*/);
-    BSC_TRY(prim_inclusive_max_i32(x, x->f_hit, x->f_headpos, (size_t)n));
+    BSC_TRY(prim_inclusive_max_i32(lane_main(x), x->f_hit, x->f_headpos, (size_t)n));
     hipLaunchKernelGGL(k_flush_plan, grid, block, 0, s, n, x->f_keys_b, x->f_headpos, x->store_cnt, x->store_rows, cs,
                        x->dscal, x->c.token_capacity, x->f_rowdst, x->f_hit, x->f_rowseg, x->f_rowe);
     hipLaunchKernelGGL(k_flush_counts, grid, block, 0, s, n, x->f_keys_b, x->f_headpos, x->store_cnt, cs);
     hipLaunchKernelGGL(k_flush_copy, wgrid, block, 0, s, n, x->f_rowdst, x->cache_f, x->cache_d, D, x->pool, x->pool_d);
-    BSC_TRY(prim_exclusive_sum_i32(x, x->f_hit, x->f_hidx, (size_t)n));
+    BSC_TRY(prim_exclusive_sum_i32(lane_main(x), x->f_hit, x->f_hidx, (size_t)n));
     hipLaunchKernelGGL(k_flush_nhits, dim3(1), dim3(64), 0, s, n, x->f_hit, x->f_hidx, x->dscal);
     BSC_HIP(hipGetLastError());
     BSC_TRY(read_scalars(x));

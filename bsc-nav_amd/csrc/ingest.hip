@@ -8,7 +8,7 @@
 //               records by cell (stable, in LDS), emits ONE run per (block, cell) and makes one first-touch claim per cell: the
 //               smallest point index wins a still-empty cell, the claimer that found it empty lists the cell as new
 //   k_block_totals   the block scans (runs, passing points) + the batch scalars in one launch; the scalars reach the host through
-//               a mailbox in pinned memory (round 6; k_totals + two rocPRIM scans + a copy before)
+//               a mailbox in pinned memory (round 6; k_totals + two rocPRIM scans + a copy before: BSC_TOTALS_UNFUSED=1)
 //   k_patch_pairs / k_keys_pairs (dense.hip) LDS aggregation of (cell, frame, patch) pairs — independent of the ids
 //   k_new_keys + sort + k_new_assign   the new cells ranked by their winning point: id = max_id + rank, as the
 //               sequential max_id++ hands them out (a few thousand cells, not a pass over the points)
@@ -25,6 +25,7 @@
 //   k_append    exact mode: token rows into the cache in order                (1 wavefront / row)
 #include "bsc_internal.h"
 #include "geometry_dev.h"
+#include "ingest_mail.h"
 
 #include <limits.h>
 #include <sched.h>
@@ -644,12 +645,12 @@ __global__ __launch_bounds__(BT_THREADS) void k_block_totals(int64_t P, int64_t 
     bscal[5] = 0;                       // (unused)
     bscal[6] = 0;                       // hot segments (k_seg_order): the first bscal[6] of the long ones, a workgroup each
     if (mail) {
-        // write-through 8-byte stores to the host, EVERY word tagged with the call's sequence number (value << 16 | seq: the scalars
-        // are counts below 2^47): the host takes the mailbox once all words carry the tag, whatever order the fabric delivered them
+        // write-through 8-byte stores to the host, EVERY word tagged with the call's sequence number (ingest_mail.h: value << 16 | seq,
+        // the scalars are counts below 2^47): the host takes the mailbox once all words carry the tag, whatever order the fabric delivered them
         // in — no release fence (at system scope it writes back the whole L2), no ordering assumed between posted writes
 #pragma unroll
         for (int k = 0; k < DS_COUNT; ++k)
-            __hip_atomic_store(&mail[k], (int64_t)(((u64)d[k] << 16) | ((u64)seq & 0xffffull)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&mail[k], mail_encode(d[k], (uint64_t)seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -1037,6 +1038,7 @@ __device__ __forceinline__ uint32_t rec_rgb(const RecT<true> &t) { return t.r.x 
 // positions [64 w, 64 w + 64); ck_run[w] / ck_start[w] name the (sorted) run that covers position 64 w and where it starts, so a
 // lookup is stateless: one word, one checkpoint, one gather of j0 — any position, any order, no running count.
 struct RunOrder { const u64 *bits; const uint32_t *ck_run, *ck_start, *j0; };
+static inline RunOrder run_order_of(const IngestSet &S) { return {S.run_bits, S.ck_run, S.ck_start, S.run_val}; }
 struct RunLook { u64 b; uint32_t r, s; };             // what the word of a position holds (loaded ahead of its use)
 __device__ __forceinline__ RunLook run_look(const RunOrder &o, int64_t k)
 {
@@ -1746,10 +1748,11 @@ bsc_status launch_geometry_debug(bsc_ctx *x, const float *depth, const int32_t *
 // launches the rgb chain + top-down map kernels of the last ingest call, if they have not been launched yet
 bsc_status launch_pending_chain(bsc_ctx *x)
 {
-    if (!x->chain_pending) return BSC_OK;
-    x->chain_pending = false;
-    const int set = x->chain_set;
-    BSC_HIP(hipStreamWaitEvent(x->side, x->ev_ready[set], 0));
+    if (!x->chain.pending) return BSC_OK;
+    x->chain.pending = false;
+    const int set = x->chain.set;
+    IngestSet &S = x->set[set];
+    BSC_HIP(hipStreamWaitEvent(x->side, S.ev_ready, 0));
     // A call followed at once by bsc_sync (the isolated call of the bench, a frame-by-frame user): the chain would start beside the
     // pair sort of the same call, whose look-back tiles then wait for CUs the chain's resident workgroups hold (pair sort 0.3 ->
     // 0.7 ms with two 8-wavefront chain workgroups per CU).  Behind the pair sort it overlaps the dense reduce alone.  In a pipeline
@@ -1766,27 +1769,27 @@ bsc_status launch_pending_chain(bsc_ctx *x)
     // per SIMD (workgroups of 8) slow the tail itself: 6 -> 9 ms.
     stat_begin(x, BSC_STAT_CHAIN, x->side);
     static const int chain_waves = getenv("BSC_CHAIN_WAVES") ? atoi(getenv("BSC_CHAIN_WAVES")) : CHAIN_WAVES;
-    const bool rec8 = x->rec8_s[set];           // the record format of the call whose chain this is
+    const bool rec8 = S.rec8;                   // the record format of the call whose chain this is
     const GeomConst gc = make_geom_const(x);
 #define BSC_LAUNCH_CHAIN(R8)                                                                                                    \
-    hipLaunchKernelGGL(k_chain<R8>, dim3(chain_waves * 64 / CHAIN_WG), dim3(CHAIN_WG), 0, x->side, gc, x->sval_b_s[set],         \
-                       x->bscal_s[set], x->seg_info_s[set], (const void *)x->p_rec_s[set], x->rgb_pos, x->rgb, x->weight, x->hmap, \
-                       x->seg_last_s[set], x->c.grid_size, x->chain_order_base)
+    hipLaunchKernelGGL(k_chain<R8>, dim3(chain_waves * 64 / CHAIN_WG), dim3(CHAIN_WG), 0, x->side, gc, S.sval_b, S.bscal,        \
+                       S.seg_info, (const void *)S.p_rec, x->rgb_pos, x->rgb, x->weight, x->hmap, S.seg_last, x->c.grid_size,   \
+                       x->chain.order_base)
     if (rec8) BSC_LAUNCH_CHAIN(true); else BSC_LAUNCH_CHAIN(false);
 #undef BSC_LAUNCH_CHAIN
     static const int long_waves = getenv("BSC_LONG_WAVES") ? atoi(getenv("BSC_LONG_WAVES")) : LONG_WAVES;
     // a wavefront per ~4096 points of the batch, at most long_waves (a frame-by-frame call launches a handful)
-    int64_t nw = x->chain_points / 4096;
+    int64_t nw = x->chain.points / 4096;
     nw = nw < 64 ? 64 : (nw > long_waves ? long_waves : nw);
     // 8 wavefronts per hot segment since round 6 (two workgroups per CU: one steps its rounds while the other waits for records or
     // at a barrier): chain 2.55 -> 1.95 ms per 768-frame call against the 16-wavefront form
     static const int long_nwv = getenv("BSC_LONG_NWV") ? atoi(getenv("BSC_LONG_NWV")) : 8;
     if (x->long_chain) {
-        const RunOrder ro = {x->run_bits_s[set], x->ck_run_s[set], x->ck_start_s[set], x->run_val_s[set]};
+        const RunOrder ro = run_order_of(S);
 #define BSC_LAUNCH_LONG(NWVV, R8, PARTV, GRID, ST)                                                                              \
-    hipLaunchKernelGGL((k_chain_long<NWVV, R8, PARTV>), dim3((unsigned)(GRID)), dim3(NWVV * 64), 0, ST, gc, ro,                  \
-                       x->bscal_s[set], x->seg_info_s[set], (const void *)x->p_rec_s[set], x->rgb_pos, x->rgb, x->weight,        \
-                       x->hmap, x->seg_last_s[set], x->c.grid_size, x->chain_order_base)
+    hipLaunchKernelGGL((k_chain_long<NWVV, R8, PARTV>), dim3((unsigned)(GRID)), dim3(NWVV * 64), 0, ST, gc, ro, S.bscal,         \
+                       S.seg_info, (const void *)S.p_rec, x->rgb_pos, x->rgb, x->weight, x->hmap, S.seg_last, x->c.grid_size,   \
+                       x->chain.order_base)
         // round 6: the one-wavefront segments (three quarters of the room scene's points) as a launch of their own, at the occupancy
         // a chain of dependent steps needs, on a second side stream beside the hot tiles (BSC_CHAIN_SPLIT=0: one launch for both)
         static const bool chain_split = getenv("BSC_CHAIN_SPLIT") == nullptr || atoi(getenv("BSC_CHAIN_SPLIT")) != 0;
@@ -1794,7 +1797,7 @@ bsc_status launch_pending_chain(bsc_ctx *x)
             BSC_HIP(hipEventRecord(x->ev_chain0, x->side));                 // behind k_chain: the first points of the new voxels
             BSC_HIP(hipStreamWaitEvent(x->side2, x->ev_chain0, 0));
             // a workgroup per hot segment (the device counts them; the host bounds them by the points of the call), launched first
-            int64_t ghot = x->chain_points >> HOT_MIN_LOG2;
+            int64_t ghot = x->chain.points >> HOT_MIN_LOG2;
             ghot = ghot < 1 ? 1 : (ghot > 2048 ? 2048 : ghot);
             if (rec8) BSC_LAUNCH_LONG(8, true, 1, ghot, x->side); else BSC_LAUNCH_LONG(8, false, 1, ghot, x->side);
             const int64_t gmid = (nw + 3) / 4;
@@ -1806,15 +1809,260 @@ bsc_status launch_pending_chain(bsc_ctx *x)
 #undef BSC_LAUNCH_LONG
     }
 #define BSC_LAUNCH_HWIN(R8)                                                                                                     \
-    hipLaunchKernelGGL(k_hwin<R8>, dim3(256), dim3(TPB), 0, x->side, x->bscal_s[set], x->seg_info_s[set], x->seg_last_s[set],    \
-                       x->rgb_pos, x->hmap, (const void *)x->p_rec_s[set], x->cv_map, x->c.grid_size, x->chain_order_base)
+    hipLaunchKernelGGL(k_hwin<R8>, dim3(256), dim3(TPB), 0, x->side, S.bscal, S.seg_info, S.seg_last, x->rgb_pos, x->hmap,       \
+                       (const void *)S.p_rec, x->cv_map, x->c.grid_size, x->chain.order_base)
     if (rec8) BSC_LAUNCH_HWIN(true); else BSC_LAUNCH_HWIN(false);
 #undef BSC_LAUNCH_HWIN
     stat_end(x, BSC_STAT_CHAIN, 0.0, x->side);
-    BSC_HIP(hipEventRecord(x->ev_done[set], x->side));
-    x->ev_done_valid[set] = true;
+    BSC_HIP(hipEventRecord(S.ev_done, x->side));
+    S.ev_done_valid = true;
     x->last_chain_set = set;
     BSC_HIP(hipGetLastError());
+    return BSC_OK;
+}
+
+// ---- the host driver of bsc_ingest ------------------------------------------------------------------------------------------------
+// One call = a front end on the main stream (k_points, k_block_totals, the pair tiles), a readback of the batch counts the back
+// end is sized from, the ids of the new voxels, the ORDER STAGE (k_run_keys .. k_expand_short: the per-voxel point order, which
+// feeds only the rgb chain) and the mode's back end (dense reduce / token cache).  The order stage and the back end are chains of
+// short memory-bound kernels with launch gaps between them; side by side each fills the other's gaps (own sort workspaces: the
+// PrimLane of the stream, disjoint buffers).  Where the order stage runs, and how the streams hand over, is the call's schedule:
+//
+//   SCHED_EARLY   dense modes, order stage on the side stream (the default of the dense modes)
+//       main   front end; RECORD ev_tot behind k_block_totals; pair tiles; copy of the pair count; ... synchronize (the pair
+//              count); WAIT ev_ids; dense reduce
+//       host   the counts arrive WHILE the main stream runs the pair tiles: through the mailbox k_block_totals writes, or over the
+//              copy stream (WAIT ev_tot, copy, synchronize)
+//       side   WAIT ev_tot; new ids; RECORD ev_ids; order stage (RECORD ev_runs behind k_run_keys); RECORD ev_ready
+//              With ONE readback after the pair tiles the host came back to an empty main stream and spent ~0.26 ms enqueueing
+//              before it had work again, and the order stage (hence the rgb chain) started 0.45 ms late.
+//       a refused call (voxel capacity): side WAIT ev_tot, new ids, RECORD ev_ids; main WAIT ev_ids
+//   SCHED_SIDE    exact mode, order stage on the side stream (the default of exact mode)
+//       main   front end; pair tiles (none in exact mode); read_scalars (copy + synchronize); WAIT ev_ready of the last order stage
+//              on the side stream (it shares the run keys / values and their sort outputs with the ids); new ids; RECORD ev_ids;
+//              ... WAIT ev_runs (k_append reads the pass list k_pass_list wrote); k_append / flushes
+//       side   WAIT ev_ids; order stage (RECORD ev_runs behind k_run_keys / k_pass_list); RECORD ev_ready
+//   SCHED_MAIN    BSC_ORDER_MAIN=1, either mode: one stream, as in round 2
+//       main   front end; pair tiles; read_scalars; new ids; dense reduce (dense modes); order stage; RECORD ev_ready;
+//              k_append / flushes (exact mode)
+//   every schedule, at the start of the call: the previous call's rgb chain is launched on the side stream (launch_pending_chain);
+//   main WAITS ev_done of the call's scratch set (the chain of the call before last may still read it) and ev_runs (the last side
+//   order stage is done with p_cell / the block offsets).  The call's own chain is deferred: see the end of ingest_batch.
+enum IngestSched { SCHED_MAIN, SCHED_SIDE, SCHED_EARLY };
+
+struct IngestCall {             // what the stages of one call share
+    bsc_ctx *x;
+    IngestSet *S;               // scratch set of this call
+    IngestSched sched;
+    PrimLane main, order;       // the main stream; where the order stage runs
+    int64_t P, nblk;            // points; k_points workgroups
+    int n_frames, vb;           // vb: bits of the voxel id field in a run key
+    bool exact;
+};
+
+// k_points, the block totals (+ batch scalars) and the pair tiles, on the main stream; *mailbox: the scalars leave through the mailbox
+static bsc_status ingest_front_end(const IngestCall &c, const float *depth, const uint8_t *rgb, int32_t rgb_ch, const int32_t *idx,
+                                   const int64_t *offsets_host, const double *alpha, bool *mailbox)
+{
+    bsc_ctx *const x = c.x;
+    IngestSet &S = *c.S;
+    const hipStream_t s = c.main.stream;
+    const int64_t N = (int64_t)x->c.height * x->c.width, P = c.P;
+    const int n_frames = c.n_frames;
+    const dim3 block(TPB), fgrid((unsigned)c.nblk);
+    if (idx)
+        BSC_HIP(hipMemcpyAsync(x->d_offsets, offsets_host, sizeof(int64_t) * (n_frames + 1), hipMemcpyHostToDevice, s));
+    BSC_HIP(hipMemsetAsync(x->dscal + DS_B_NNEW, 0, sizeof(int64_t), s));
+    GeomConst gc = make_geom_const(x);
+    // a run's length travels in the key bits beside the voxel id: the id field is sized for the voxel capacity, the
+    // rest (at most 10 bits) holds length - 1; k_points cuts longer groups into several runs
+    const int lb = 32 - c.vb < 10 ? 32 - c.vb : 10;
+    const bool all_px_dense = !c.exact && idx == nullptr && x->geom_fast;     // the patch comes from the pixel: no p_patf
+    uint32_t *patf = all_px_dense ? (uint32_t *)nullptr : x->p_patf;
+    float *r2f = c.exact ? x->p_r2f : (float *)nullptr;
+    const float inv_w = 1.0f / (float)x->c.width;
+    int32_t *g_cell = x->log_cap ? x->log_cell + x->log_n : (int32_t *)nullptr;    // bsc_point_log_*: cells in record order
+    stat_begin(x, BSC_STAT_INGEST);
+    stat_begin(x, BSC_STAT_POINTS);
+#define BSC_LAUNCH_POINTS(FASTV, RPWV, PLAINV, R8)                                                                             \
+    hipLaunchKernelGGL((k_points<FASTV, RPWV, PLAINV, R8>), fgrid, block, 0, s, gc, depth, rgb, rgb_ch, idx, x->d_offsets, n_frames, \
+                       x->d_transforms, alpha, P, inv_w, lb, x->occ, x->p_cell, patf, (void *)S.p_rec, r2f, x->new_cells, x->dscal, \
+                       x->blk_cnt, x->blk_pass, x->stage_cell, x->stage_pos, g_cell)
+    // (PLAIN also takes for granted that every pixel lies inside the patch grid — bsc_create checked the tables — and reads none)
+    // and that a frame is a whole number of wavefront slices (RPW x 64 points: 640x480 = 600 x 512), so that a wavefront never
+    // crosses into the next frame and its transform stays what it loaded at the start: with the conditional reload inside the
+    // rounds the compiler waited for EVERY load in flight at the head of each round — the previous round's colour gather included
+    const bool plain = !idx && !patf && !r2f && !alpha && !g_cell && x->pat_all_in && N % (x->group_rpw * 64) == 0 && x->c.width >= 64;
+    // 8-byte records {rgb, index in block, depth offset} where the depth range allows (bsc_create), alpha left to the rgb chain
+    const bool rec8 = gc.fast && plain && x->rec8_ok;
+    S.rec8 = rec8;
+#define BSC_LAUNCH_POINTS_R(FASTV, PLAINV, R8)                                                                                 \
+    do {                                                                                                                       \
+        if (x->group_rpw == 16) BSC_LAUNCH_POINTS(FASTV, 16, PLAINV, R8);                                                      \
+        else if (x->group_rpw == 8) BSC_LAUNCH_POINTS(FASTV, 8, PLAINV, R8);                                                   \
+        else BSC_LAUNCH_POINTS(FASTV, 4, PLAINV, R8);                                                                          \
+    } while (0)
+    if (rec8) BSC_LAUNCH_POINTS_R(true, true, true);
+    else if (gc.fast && plain) BSC_LAUNCH_POINTS_R(true, true, false);
+    else if (gc.fast) BSC_LAUNCH_POINTS_R(true, false, false);
+    else BSC_LAUNCH_POINTS_R(false, false, false);
+#undef BSC_LAUNCH_POINTS_R
+#undef BSC_LAUNCH_POINTS
+    stat_end(x, BSC_STAT_POINTS, 0.0);
+    if (x->log_cap)             // the call's records, block-grouped like p_rec (every voxel's points still in order j)
+        BSC_HIP(hipMemcpyAsync(x->log_rec + x->log_n, S.p_rec, sizeof(PointRec) * (size_t)P, hipMemcpyDeviceToDevice, s));
+    static const bool fused_totals = getenv("BSC_TOTALS_UNFUSED") == nullptr;
+    *mailbox = fused_totals && c.sched == SCHED_EARLY && x->mail != nullptr;
+    if (fused_totals) {
+        x->mail_seq += 1;
+        hipLaunchKernelGGL(k_block_totals, dim3(1), dim3(BT_THREADS), 0, s, P, c.nblk, x->blk_cnt, x->blk_off, x->blk_pass, x->blk_pass_off,
+                           x->dscal, x->c.voxel_capacity, S.bscal, *mailbox ? x->mail_dev : (int64_t *)nullptr, x->mail_seq);
+    } else {
+        BSC_TRY(prim_exclusive_sum_i32(c.main, x->blk_cnt, x->blk_off, (size_t)c.nblk));
+        BSC_TRY(prim_exclusive_sum_i32(c.main, x->blk_pass, x->blk_pass_off, (size_t)c.nblk));
+        hipLaunchKernelGGL(k_totals, dim3(1), dim3(64), 0, s, P, c.nblk, x->blk_cnt, x->blk_off, x->blk_pass, x->blk_pass_off, x->dscal,
+                           x->c.voxel_capacity, S.bscal);
+    }
+    if (c.sched == SCHED_EARLY) BSC_HIP(hipEventRecord(x->ev_tot, s));
+    stat_begin(x, BSC_STAT_PAIRS);
+    BSC_TRY(launch_keys_pairs(x, P, n_frames, idx == nullptr, patf));
+    stat_end(x, BSC_STAT_PAIRS, 0.0);
+    return BSC_OK;
+}
+
+// One small readback per call -> x->hscal: new voxels, runs, pairs (dense modes), passing points (exact mode), capacity flag.
+// Everything enqueued so far is the call's front end; the back end is sized from these numbers.
+static bsc_status read_batch_counts(const IngestCall &c, bool mailbox)
+{
+    bsc_ctx *const x = c.x;
+    const hipStream_t s = c.main.stream;
+    if (c.sched != SCHED_EARLY) return read_scalars(x);
+    // the pair count: copied behind the pair tiles right away (its own pinned slot), waited for after the side stream's launches
+    BSC_HIP(hipMemcpyAsync(x->hscal + DS_COUNT, x->dscal + DS_B_NPAIR, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    bool got = false;
+    if (mailbox) {
+        // the scalars arrive in the mailbox behind k_block_totals; spin on its sequence number (bounded: a failed launch or a
+        // lost device never writes it — after ~2 s fall back to the copy, which reports the error)
+        static_assert(DS_COUNT <= MAIL_MAX_WORDS, "mail_take holds the mailbox on its stack");
+        const volatile int64_t *const mb = x->mail;
+        const uint64_t seq = (uint64_t)x->mail_seq;
+        for (int64_t spin = 0; spin < (1ll << 31); ++spin) {
+            if (mail_tagged(__atomic_load_n(&mb[DS_COUNT - 1], __ATOMIC_ACQUIRE), seq) && mail_take(mb, DS_COUNT, seq, x->hscal)) { got = true; break; }
+            if ((spin & 1023) == 1023) sched_yield();       // behind a caller's encoder pass the wait is long: let other threads run
+            if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(s) != hipErrorNotReady) { got = mail_take(mb, DS_COUNT, seq, x->hscal); break; }
+        }
+    }
+    if (!got) {
+        BSC_HIP(hipStreamWaitEvent(x->copy, x->ev_tot, 0));
+        BSC_HIP(hipMemcpyAsync(x->hscal, x->dscal, sizeof(int64_t) * DS_COUNT, hipMemcpyDeviceToHost, x->copy));
+        BSC_HIP(hipStreamSynchronize(x->copy));
+    }
+    return BSC_OK;
+}
+
+// ids of the new voxels: rank of their winning point among the winners (memory_2.py:888-894)
+static bsc_status assign_new_ids(const IngestCall &c, const PrimLane &lane)
+{
+    bsc_ctx *const x = c.x;
+    const int64_t n_new_listed = x->hscal[DS_B_NNEW], n_new = x->hscal[DS_B_NFIRST];
+    if (n_new_listed > 0) {
+        const dim3 block(TPB), ngrid((unsigned)((n_new_listed + TPB - 1) / TPB));
+        hipLaunchKernelGGL(k_new_keys, ngrid, block, 0, lane.stream, n_new_listed, x->new_cells, x->occ, x->skey_a, x->sval_a);
+        BSC_TRY(prim_sort_pairs_u32(lane, x->skey_a, c.S->skey_b, x->sval_a, x->run_val_b, (size_t)n_new_listed, 0,
+                                    ceil_log2_u64((uint64_t)c.P + 1)));
+        hipLaunchKernelGGL(k_new_assign, ngrid, block, 0, lane.stream, n_new_listed, n_new, x->run_val_b, x->occ, x->dscal,
+                           x->c.grid_size, x->nh, x->rgb_pos);
+    }
+    return BSC_OK;
+}
+
+// The per-voxel point order of the call (k_run_keys .. k_expand_short) into its scratch set, on the lane's stream
+static bsc_status order_stage(const IngestCall &c, const PrimLane &lane)
+{
+    bsc_ctx *const x = c.x;
+    IngestSet &S = *c.S;
+    const hipStream_t so = lane.stream;
+    const int64_t P = c.P, nblk = c.nblk;
+    const int vb = c.vb;
+    const dim3 block(TPB), fgrid((unsigned)nblk);
+    stat_begin(x, BSC_STAT_ORDER, so);
+    // stable radix sort of the RUNS on the voxel id alone: runs enter in order j, so each voxel's runs stay in order;
+    // their expansion is the per-voxel point order
+    const int64_t R = x->hscal[DS_B_NRUN];
+    {
+        const dim3 rgrid((unsigned)((nblk + TPB / 64 - 1) / (TPB / 64)));
+#define BSC_LAUNCH_RUN_KEYS(GBV)                                                                                               \
+    do {                                                                                                                       \
+        hipLaunchKernelGGL(k_run_keys<GBV>, rgrid, block, 0, so, nblk, vb, x->stage_cell, x->stage_pos, x->occ, x->blk_cnt,    \
+                           x->blk_off, x->blk_pass, x->skey_a, x->sval_a);                                                     \
+        if (c.exact) hipLaunchKernelGGL(k_pass_list<GBV>, fgrid, block, 0, so, P, x->p_cell, x->blk_pass_off, x->pass_list);   \
+    } while (0)
+        if (x->group_rpw == 16) BSC_LAUNCH_RUN_KEYS(4096);
+        else if (x->group_rpw == 8) BSC_LAUNCH_RUN_KEYS(2048);
+        else BSC_LAUNCH_RUN_KEYS(1024);
+#undef BSC_LAUNCH_RUN_KEYS
+    }
+    if (c.sched != SCHED_MAIN) { BSC_HIP(hipEventRecord(x->ev_runs, so)); x->ev_runs_valid = true; }
+    // ids in use are < max_id; runs without a voxel carry an all-ones id field, which sorts last under the bit mask
+    const int vid_bits = ceil_log2_u64((uint64_t)x->hscal[DS_MAX_ID] + 2);
+    if (R > 0) {        // a batch without a single passing point has no runs (k_block_totals left the segment count at 0)
+        BSC_TRY(sort_pairs_u32(x, lane, x->skey_a, S.skey_b, x->sval_a, S.run_val, (size_t)R, 0, vid_bits < vb ? vid_bits : vb));
+        const int64_t neb = (R + EB - 1) / EB;
+        hipLaunchKernelGGL(k_run_blocksum, dim3((unsigned)neb), block, 0, so, R, vb, S.skey_b, x->run_scan);
+        BSC_TRY(prim_exclusive_sum_i64(lane, x->run_scan, x->run_scan + neb, (size_t)neb));
+        BSC_HIP(hipMemsetAsync(S.run_bits, 0, sizeof(u64) * (size_t)((P >> 6) + 2), so));
+        hipLaunchKernelGGL(k_expand, dim3((unsigned)neb), block, 0, so, R, vb, S.skey_b, x->run_scan + neb, S.run_bits, S.ck_run,
+                           S.ck_start, x->seg_k0, x->seg_vid, S.bscal);
+    }
+    const int64_t seg_cap = (x->c.max_points < x->c.voxel_capacity ? x->c.max_points : x->c.voxel_capacity) + 1;
+    int64_t n_bound = R < x->hscal[DS_MAX_ID] ? R : x->hscal[DS_MAX_ID];     // segments <= runs, <= voxels
+    if (n_bound > seg_cap) n_bound = seg_cap;
+    hipLaunchKernelGGL(k_seg_bounds, dim3(64), block, 0, so, S.bscal, n_bound, x->seg_k0, x->seg_vid, S.seg_info, x->skey_a, x->sval_a);
+    if (n_bound > 0)
+        BSC_TRY(sort_pairs_u32(x, lane, x->skey_a, (uint32_t *)x->seg_k0, x->sval_a, (uint32_t *)x->seg_vid, (size_t)n_bound, 0, 6));
+    static const int long_log2 = getenv("BSC_LONG_LOG2") ? atoi(getenv("BSC_LONG_LOG2")) : LONG_MIN_LOG2;
+    static const int hot_log2 = getenv("BSC_NO_HOT_SPLIT") ? 0 : (getenv("BSC_HOT_LOG2") ? atoi(getenv("BSC_HOT_LOG2")) : HOT_MIN_LOG2);
+    hipLaunchKernelGGL(k_seg_order, dim3(64), block, 0, so, S.bscal, (const uint32_t *)x->seg_k0, (const uint32_t *)x->seg_vid,
+                       S.seg_info, x->long_chain ? long_log2 : 0, hot_log2);
+    if (R > 0) {
+        // order indices for the quad chain: everything when there is no long chain (bscal[4] stays 0)
+        int64_t nw = P / 1024;
+        nw = nw < 64 ? 64 : (nw > 4096 ? 4096 : nw);
+        hipLaunchKernelGGL(k_expand_short, dim3((unsigned)((nw + TPB / 64 - 1) / (TPB / 64))), block, 0, so, S.bscal, S.seg_info,
+                           run_order_of(S), S.sval_b, LONG_EARLY);
+    }
+    stat_end(x, BSC_STAT_ORDER, 0.0, so);
+    return BSC_OK;
+}
+
+// exact mode, memory_2.py:880-886: rows fill the cache in order; the point that finds it full triggers the
+// flush (:881, the policy of bsc_set_flush_policy) and loses its own token.
+static bsc_status append_exact(bsc_ctx *x, const void *tokens, int token_dtype, bsc_draw_fn draw, void *user)
+{
+    const dim3 block(TPB);
+    int64_t remaining = x->hscal[DS_B_NPASS], q = 0;
+    while (remaining > 0) {
+        const int64_t room = x->c.iter_size - x->iter_id;
+        const int64_t n = remaining < room ? remaining : room;
+        if (n > 0) {
+            const dim3 agrid((unsigned)((n * 64 + TPB - 1) / TPB));
+            if (token_dtype == BSC_TOK_BF16)
+                hipLaunchKernelGGL(k_append<bf16_t>, agrid, block, 0, x->stream, x->pass_list, q, n, x->iter_id, x->p_cell,
+                                   x->p_patf, x->p_r2f, (const bf16_t *)tokens, x->g2, x->c.token_dim, x->c.grid_size,
+                                   x->nh, x->cache_f, x->cache_pos, x->cache_d);
+            else
+                hipLaunchKernelGGL(k_append<float>, agrid, block, 0, x->stream, x->pass_list, q, n, x->iter_id, x->p_cell,
+                                   x->p_patf, x->p_r2f, (const float *)tokens, x->g2, x->c.token_dim, x->c.grid_size,
+                                   x->nh, x->cache_f, x->cache_pos, x->cache_d);
+            BSC_HIP(hipGetLastError());
+            x->iter_id += n; q += n; remaining -= n;
+        }
+        if (remaining > 0) {        // next passing point meets a full cache
+            if (x->flush_policy == BSC_FLUSH_SURPRISE) BSC_TRY(surprise_flush(x, x->fp_radius, x->fp_sthr, x->fp_bthr));
+            else BSC_TRY(flush_cache(x, draw, user));
+            q += 1; remaining -= 1;
+        }
+    }
     return BSC_OK;
 }
 
@@ -1833,246 +2081,65 @@ bsc_status ingest_batch(bsc_ctx *x, int32_t n_frames, const float *depth, const 
         bsc_set_error("bsc_ingest: point log full (%lld + %lld > %lld points)", (long long)x->log_n, (long long)P, (long long)x->log_cap);
         return BSC_E_CAPACITY;
     }
-    const dim3 block(TPB);
-    hipStream_t s = x->stream;
-    const bool exact = x->c.mode == BSC_MODE_EXACT;
     BSC_TRY(launch_pending_chain(x));          // the previous call's rgb chain runs beside this call's front end
     // scratch set of this call; the rgb chain of the call before last may still be reading it on the side stream
     const int set = x->cur_set;
     x->cur_set ^= 1;
-    if (x->ev_done_valid[set]) BSC_HIP(hipStreamWaitEvent(s, x->ev_done[set], 0));
-    if (x->ev_runs_valid) BSC_HIP(hipStreamWaitEvent(s, x->ev_runs, 0));      // the last call's k_runs (side stream) is done with p_cell / blk_off
-    PointRec *p_rec = x->p_rec_s[set];
-    uint32_t *skey_b = x->skey_b_s[set];
-    if (idx)
-        BSC_HIP(hipMemcpyAsync(x->d_offsets, offsets_host, sizeof(int64_t) * (n_frames + 1), hipMemcpyHostToDevice, s));
-    BSC_HIP(hipMemsetAsync(x->dscal + DS_B_NNEW, 0, sizeof(int64_t), s));
-    GeomConst gc = make_geom_const(x);
-    // a run's length travels in the key bits beside the voxel id: the id field is sized for the voxel capacity, the
-    // rest (at most 10 bits) holds length - 1; k_points cuts longer groups into several runs
-    const int vb = ceil_log2_u64((uint64_t)x->c.voxel_capacity + 2);
-    const int lb = 32 - vb < 10 ? 32 - vb : 10;
+    const bool exact = x->c.mode == BSC_MODE_EXACT;
+    const IngestSched sched = !x->order_on_side ? SCHED_MAIN : (exact ? SCHED_SIDE : SCHED_EARLY);
     const int GBP = x->group_rpw * 256;                 // points per k_points workgroup
-    const int64_t nblk = (P + GBP - 1) / GBP;
-    const dim3 fgrid((unsigned)nblk);
-    const bool all_px_dense = !exact && idx == nullptr && x->geom_fast;     // the patch comes from the pixel: no p_patf
-    uint32_t *patf = all_px_dense ? (uint32_t *)nullptr : x->p_patf;
-    float *r2f = exact ? x->p_r2f : (float *)nullptr;
-    const float inv_w = 1.0f / (float)x->c.width;
-    int32_t *g_cell = x->log_cap ? x->log_cell + x->log_n : (int32_t *)nullptr;    // bsc_point_log_*: cells in record order
-    stat_begin(x, BSC_STAT_INGEST);
-    stat_begin(x, BSC_STAT_POINTS);
-#define BSC_LAUNCH_POINTS(FASTV, RPWV, PLAINV, R8)                                                                             \
-    hipLaunchKernelGGL((k_points<FASTV, RPWV, PLAINV, R8>), fgrid, block, 0, s, gc, depth, rgb, rgb_ch, idx, x->d_offsets, n_frames, \
-                       x->d_transforms, alpha, P, inv_w, lb, x->occ, x->p_cell, patf, (void *)p_rec, r2f, x->new_cells, x->dscal, \
-                       x->blk_cnt, x->blk_pass, x->stage_cell, x->stage_pos, g_cell)
-    // (PLAIN also takes for granted that every pixel lies inside the patch grid — bsc_create checked the tables — and reads none)
-    // and that a frame is a whole number of wavefront slices (RPW x 64 points: 640x480 = 600 x 512), so that a wavefront never
-    // crosses into the next frame and its transform stays what it loaded at the start: with the conditional reload inside the
-    // rounds the compiler waited for EVERY load in flight at the head of each round — the previous round's colour gather included
-    const bool plain = !idx && !patf && !r2f && !alpha && !g_cell && x->pat_all_in && N % (x->group_rpw * 64) == 0 && x->c.width >= 64;
-    // 8-byte records {rgb, index in block, depth offset} where the depth range allows (bsc_create), alpha left to the rgb chain
-    const bool rec8 = gc.fast && plain && x->rec8_ok;
-    x->rec8_s[set] = rec8;
-#define BSC_LAUNCH_POINTS_R(FASTV, PLAINV, R8)                                                                                 \
-    do {                                                                                                                       \
-        if (x->group_rpw == 16) BSC_LAUNCH_POINTS(FASTV, 16, PLAINV, R8);                                                      \
-        else if (x->group_rpw == 8) BSC_LAUNCH_POINTS(FASTV, 8, PLAINV, R8);                                                   \
-        else BSC_LAUNCH_POINTS(FASTV, 4, PLAINV, R8);                                                                          \
-    } while (0)
-    if (rec8) BSC_LAUNCH_POINTS_R(true, true, true);
-    else if (gc.fast && plain) BSC_LAUNCH_POINTS_R(true, true, false);
-    else if (gc.fast) BSC_LAUNCH_POINTS_R(true, false, false);
-    else BSC_LAUNCH_POINTS_R(false, false, false);
-#undef BSC_LAUNCH_POINTS_R
-#undef BSC_LAUNCH_POINTS
-    stat_end(x, BSC_STAT_POINTS, 0.0);
-    if (x->log_cap)             // the call's records, block-grouped like p_rec (every voxel's points still in order j)
-        BSC_HIP(hipMemcpyAsync(x->log_rec + x->log_n, p_rec, sizeof(PointRec) * (size_t)P, hipMemcpyDeviceToDevice, s));
-    static const bool fused_totals = getenv("BSC_TOTALS_UNFUSED") == nullptr;
-    const bool early = x->order_on_side && !exact;
-    const bool mailbox = fused_totals && early && x->mail != nullptr;
-    if (fused_totals) {
-        x->mail_seq += 1;
-        hipLaunchKernelGGL(k_block_totals, dim3(1), dim3(BT_THREADS), 0, s, P, nblk, x->blk_cnt, x->blk_off, x->blk_pass, x->blk_pass_off,
-                           x->dscal, x->c.voxel_capacity, x->bscal_s[set], mailbox ? x->mail_dev : (int64_t *)nullptr, x->mail_seq);
-    } else {
-        BSC_TRY(prim_exclusive_sum_i32(x, x->blk_cnt, x->blk_off, (size_t)nblk));
-        BSC_TRY(prim_exclusive_sum_i32(x, x->blk_pass, x->blk_pass_off, (size_t)nblk));
-        hipLaunchKernelGGL(k_totals, dim3(1), dim3(64), 0, s, P, nblk, x->blk_cnt, x->blk_off, x->blk_pass, x->blk_pass_off, x->dscal,
-                           x->c.voxel_capacity, x->bscal_s[set]);
-    }
-    // early: (dense modes, order stage on the side stream) the counts k_totals wrote come back over a copy stream WHILE the main
-    // stream runs the pair tiles, and the new-voxel ids + order stage are enqueued on the side stream during that time; the pair
-    // count follows with a second, short readback.  With ONE readback after the pair tiles the host came back to an empty main
-    // stream and spent ~0.26 ms enqueueing before it had work again, and the order stage (hence the rgb chain) started 0.45 ms late.
-    if (early) BSC_HIP(hipEventRecord(x->ev_tot, s));
-    stat_begin(x, BSC_STAT_PAIRS);
-    BSC_TRY(launch_keys_pairs(x, P, n_frames, idx == nullptr, patf));
-    stat_end(x, BSC_STAT_PAIRS, 0.0);
-    // one small readback per call: new voxels, runs, pairs (dense modes), passing points (exact mode), capacity flag.
-    // Everything enqueued so far is the call's front end; the back end is sized from these numbers.
-    if (early) {
-        // the pair count: copied behind the pair tiles right away (its own pinned slot), waited for after the side stream's launches
-        BSC_HIP(hipMemcpyAsync(x->hscal + DS_COUNT, x->dscal + DS_B_NPAIR, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        bool got = false;
-        if (mailbox) {
-            // the scalars arrive in the mailbox behind k_block_totals; spin on its sequence number (bounded: a failed launch or a
-            // lost device never writes it — after ~2 s fall back to the copy, which reports the error)
-            volatile int64_t *const mb = x->mail;
-            const u64 tag = (u64)x->mail_seq & 0xffffull;
-            const auto all_tagged = [&]() {
-                for (int k = 0; k < DS_COUNT; ++k)
-                    if (((u64)__atomic_load_n(&mb[k], __ATOMIC_ACQUIRE) & 0xffffull) != tag) return false;
-                return true;
-            };
-            for (int64_t spin = 0; spin < (1ll << 31); ++spin) {
-                if (((u64)__atomic_load_n(&mb[DS_COUNT - 1], __ATOMIC_ACQUIRE) & 0xffffull) == tag && all_tagged()) { got = true; break; }
-                if ((spin & 1023) == 1023) sched_yield();       // behind a caller's encoder pass the wait is long: let other threads run
-                if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(s) != hipErrorNotReady) { got = all_tagged(); break; }
-            }
-            if (got) for (int k = 0; k < DS_COUNT; ++k) x->hscal[k] = (int64_t)mb[k] >> 16;       // (arithmetic: a value in +-2^47 survives)
-        }
-        if (!got) {
-            BSC_HIP(hipStreamWaitEvent(x->copy, x->ev_tot, 0));
-            BSC_HIP(hipMemcpyAsync(x->hscal, x->dscal, sizeof(int64_t) * DS_COUNT, hipMemcpyDeviceToHost, x->copy));
-            BSC_HIP(hipStreamSynchronize(x->copy));
-        }
-    } else {
-        BSC_TRY(read_scalars(x));
-    }
-    const int64_t n_new_listed = x->hscal[DS_B_NNEW], n_new = x->hscal[DS_B_NFIRST];
-    // ids of the new voxels: rank of their winning point among the winners (memory_2.py:888-894)
-    auto assign_ids = [&](hipStream_t st) -> bsc_status {
-        if (n_new_listed > 0) {
-            const dim3 ngrid((unsigned)((n_new_listed + TPB - 1) / TPB));
-            hipLaunchKernelGGL(k_new_keys, ngrid, block, 0, st, n_new_listed, x->new_cells, x->occ, x->skey_a, x->sval_a);
-            BSC_TRY(prim_sort_pairs_u32(x, x->skey_a, skey_b, x->sval_a, x->run_val_b, (size_t)n_new_listed, 0,
-                                        ceil_log2_u64((uint64_t)P + 1)));
-            hipLaunchKernelGGL(k_new_assign, ngrid, block, 0, st, n_new_listed, n_new, x->run_val_b, x->occ, x->dscal,
-                               x->c.grid_size, x->nh, x->rgb_pos);
-        }
-        return BSC_OK;
-    };
+    const IngestCall c = {x, &x->set[set], sched, lane_main(x), sched == SCHED_MAIN ? lane_main(x) : lane_side(x), P, (P + GBP - 1) / GBP,
+                          n_frames, ceil_log2_u64((uint64_t)x->c.voxel_capacity + 2), exact};
+    const hipStream_t s = c.main.stream, so = c.order.stream;
+    const bool early = c.sched == SCHED_EARLY;
+    if (c.S->ev_done_valid) BSC_HIP(hipStreamWaitEvent(s, c.S->ev_done, 0));
+    if (x->ev_runs_valid) BSC_HIP(hipStreamWaitEvent(s, x->ev_runs, 0));      // the last call's k_run_keys / k_pass_list (side stream) are done with p_cell / blk_off
+    bool mailbox = false;
+    BSC_TRY(ingest_front_end(c, depth, rgb, rgb_ch, idx, offsets_host, alpha, &mailbox));
+    BSC_TRY(read_batch_counts(c, mailbox));
     if (!early) {
-        // The buffers the back end shares with the order stage (run keys / values and their sort outputs) may still be in use by
+        // The buffers the ids share with the order stage (run keys / values and their sort outputs) may still be in use by
         // the previous call's order stage on the side stream when calls follow each other without an encoder pass in between
-        if (x->last_order_set >= 0) BSC_HIP(hipStreamWaitEvent(s, x->ev_ready[x->last_order_set], 0));
-        BSC_TRY(assign_ids(s));
+        if (x->last_order_set >= 0) BSC_HIP(hipStreamWaitEvent(s, x->set[x->last_order_set].ev_ready, 0));
+        BSC_TRY(assign_new_ids(c, c.main));
     }
     if (x->hscal[DS_ERROR]) {
         if (early) {
-            // k_totals has already advanced max_id by the (clipped) count of new voxels: their ids are still assigned — on the side
-            // stream, as the order stage would have done — so that the map the refused call leaves behind is consistent
-            void *const keep_tmp = x->prim_tmp;
-            BSC_HIP(hipStreamWaitEvent(x->side, x->ev_tot, 0));
-            x->stream = x->side; x->prim_tmp = x->prim_tmp_side;
-            const bsc_status ist = assign_ids(x->side);
-            x->stream = s; x->prim_tmp = keep_tmp;
-            BSC_TRY(ist);
-            BSC_HIP(hipEventRecord(x->ev_ids, x->side));
+            // k_block_totals has already advanced max_id by the (clipped) count of new voxels: their ids are still assigned — on the
+            // side stream, as the order stage would have done — so that the map the refused call leaves behind is consistent
+            BSC_HIP(hipStreamWaitEvent(so, x->ev_tot, 0));
+            BSC_TRY(assign_new_ids(c, c.order));
+            BSC_HIP(hipEventRecord(x->ev_ids, so));
             BSC_HIP(hipStreamWaitEvent(s, x->ev_ids, 0));
         }
         bsc_set_error("voxel capacity %d exceeded", x->c.voxel_capacity);
         return BSC_E_CAPACITY;
     }
     if (x->log_cap) x->log_n += P;             // the log keeps the call only once it can no longer fail
-    // The per-voxel point order (k_runs .. k_seg_order) feeds only the rgb chain, which runs on the side stream anyway: it is
-    // enqueued THERE, as soon as the ids exist, and runs beside the pair sort / dense reduce of this call on the main stream.
-    // Both halves are chains of short memory-bound kernels with launch gaps between them; side by side each fills the other's
-    // gaps (own rocPRIM workspace, disjoint buffers).  BSC_ORDER_MAIN=1: one stream, as in round 2.
-    const bool side_order = x->order_on_side;
-    hipStream_t so = side_order ? x->side : s;
-    if (early) {
-        BSC_HIP(hipStreamWaitEvent(so, x->ev_tot, 0));          // the side stream takes over from k_totals: ids, then the order stage
-    } else if (side_order) {
+    // the hand-over to the order stage (the table above)
+    switch (c.sched) {
+    case SCHED_EARLY:
+        BSC_HIP(hipStreamWaitEvent(so, x->ev_tot, 0));          // the side stream takes over from k_block_totals: ids, then the order stage
+        BSC_TRY(assign_new_ids(c, c.order));
+        BSC_HIP(hipEventRecord(x->ev_ids, so));
+        break;
+    case SCHED_SIDE:
         BSC_HIP(hipEventRecord(x->ev_ids, s));
         BSC_HIP(hipStreamWaitEvent(so, x->ev_ids, 0));
-    } else if (!exact) {
-        BSC_TRY(dense_reduce_batch(x, tokens, token_dtype, n_frames));
+        break;
+    case SCHED_MAIN:
+        if (!c.exact) BSC_TRY(dense_reduce_batch(x, tokens, token_dtype, n_frames));
+        break;
     }
-    // order-pipeline launches go through the ctx's stream / workspace fields
-    void *const prim_main = x->prim_tmp;
-    if (side_order) { x->stream = so; x->prim_tmp = x->prim_tmp_side; }
-    const bsc_status order_st = [&]() -> bsc_status {
+    BSC_TRY(order_stage(c, c.order));
     if (early) {
-        BSC_TRY(assign_ids(so));
-        BSC_HIP(hipEventRecord(x->ev_ids, so));
-    }
-    stat_begin(x, BSC_STAT_ORDER, so);
-    // stable radix sort of the RUNS on the voxel id alone: runs enter in order j, so each voxel's runs stay in order;
-    // their expansion is the per-voxel point order
-    const int64_t R = x->hscal[DS_B_NRUN];
-    uint32_t *sj = x->sval_b_s[set];
-    {
-        const dim3 rgrid((unsigned)((nblk + TPB / 64 - 1) / (TPB / 64)));
-#define BSC_LAUNCH_RUN_KEYS(GBV)                                                                                               \
-    do {                                                                                                                       \
-        hipLaunchKernelGGL(k_run_keys<GBV>, rgrid, block, 0, so, nblk, vb, x->stage_cell, x->stage_pos, x->occ, x->blk_cnt,    \
-                           x->blk_off, x->blk_pass, x->skey_a, x->sval_a);                                                     \
-        if (exact) hipLaunchKernelGGL(k_pass_list<GBV>, fgrid, block, 0, so, P, x->p_cell, x->blk_pass_off, x->pass_list);     \
-    } while (0)
-        if (x->group_rpw == 16) BSC_LAUNCH_RUN_KEYS(4096);
-        else if (x->group_rpw == 8) BSC_LAUNCH_RUN_KEYS(2048);
-        else BSC_LAUNCH_RUN_KEYS(1024);
-#undef BSC_LAUNCH_RUN_KEYS
-    }
-    if (side_order) { BSC_HIP(hipEventRecord(x->ev_runs, so)); x->ev_runs_valid = true; }
-    // ids in use are < max_id; runs without a voxel carry an all-ones id field, which sorts last under the bit mask
-    const int vid_bits = ceil_log2_u64((uint64_t)x->hscal[DS_MAX_ID] + 2);
-    if (R > 0) {        // a batch without a single passing point has no runs (k_totals left the segment count at 0)
-        if (x->radix_intree)
-            BSC_TRY(radix_sort_pairs_u32(x, side_order ? &x->rx_side : &x->rx_main, so, x->skey_a, skey_b, x->sval_a, x->run_val_s[set], (size_t)R, 0,
-                                         vid_bits < vb ? vid_bits : vb));
-        else
-            BSC_TRY(prim_sort_pairs_u32(x, x->skey_a, skey_b, x->sval_a, x->run_val_s[set], (size_t)R, 0, vid_bits < vb ? vid_bits : vb));
-        const int64_t neb = (R + EB - 1) / EB;
-        hipLaunchKernelGGL(k_run_blocksum, dim3((unsigned)neb), block, 0, so, R, vb, skey_b, x->run_scan);
-        BSC_TRY(prim_exclusive_sum_i64(x, x->run_scan, x->run_scan + neb, (size_t)neb));
-        BSC_HIP(hipMemsetAsync(x->run_bits_s[set], 0, sizeof(u64) * (size_t)((P >> 6) + 2), so));
-        hipLaunchKernelGGL(k_expand, dim3((unsigned)neb), block, 0, so, R, vb, skey_b, x->run_scan + neb, x->run_bits_s[set],
-                           x->ck_run_s[set], x->ck_start_s[set], x->seg_k0, x->seg_vid, x->bscal_s[set]);
-    }
-    const int64_t seg_cap = (x->c.max_points < x->c.voxel_capacity ? x->c.max_points : x->c.voxel_capacity) + 1;
-    int64_t n_bound = R < x->hscal[DS_MAX_ID] ? R : x->hscal[DS_MAX_ID];     // segments <= runs, <= voxels
-    if (n_bound > seg_cap) n_bound = seg_cap;
-    hipLaunchKernelGGL(k_seg_bounds, dim3(64), block, 0, so, x->bscal_s[set], n_bound, x->seg_k0, x->seg_vid,
-                       x->seg_info_s[set], x->skey_a, x->sval_a);
-    if (n_bound > 0) {
-        if (x->radix_intree)
-            BSC_TRY(radix_sort_pairs_u32(x, side_order ? &x->rx_side : &x->rx_main, so, x->skey_a, (uint32_t *)x->seg_k0, x->sval_a, (uint32_t *)x->seg_vid,
-                                         (size_t)n_bound, 0, 6));
-        else
-            BSC_TRY(prim_sort_pairs_u32(x, x->skey_a, (uint32_t *)x->seg_k0, x->sval_a, (uint32_t *)x->seg_vid, (size_t)n_bound, 0, 6));
-    }
-    static const int long_log2 = getenv("BSC_LONG_LOG2") ? atoi(getenv("BSC_LONG_LOG2")) : LONG_MIN_LOG2;
-    static const int hot_log2 = getenv("BSC_NO_HOT_SPLIT") ? 0 : (getenv("BSC_HOT_LOG2") ? atoi(getenv("BSC_HOT_LOG2")) : HOT_MIN_LOG2);
-    hipLaunchKernelGGL(k_seg_order, dim3(64), block, 0, so, x->bscal_s[set], (const uint32_t *)x->seg_k0, (const uint32_t *)x->seg_vid,
-                       x->seg_info_s[set], x->long_chain ? long_log2 : 0, hot_log2);
-    if (R > 0) {
-        // order indices for the quad chain: everything when there is no long chain (bscal[4] stays 0)
-        const RunOrder ro = {x->run_bits_s[set], x->ck_run_s[set], x->ck_start_s[set], x->run_val_s[set]};
-        int64_t nw = P / 1024;
-        nw = nw < 64 ? 64 : (nw > 4096 ? 4096 : nw);
-        hipLaunchKernelGGL(k_expand_short, dim3((unsigned)((nw + TPB / 64 - 1) / (TPB / 64))), block, 0, so, x->bscal_s[set],
-                           x->seg_info_s[set], ro, sj, LONG_EARLY);
-    }
-    stat_end(x, BSC_STAT_ORDER, 0.0, so);
-    return BSC_OK;
-    }();
-    x->stream = s;
-    x->prim_tmp = prim_main;
-    BSC_TRY(order_st);
-    if (early) {
-        // the pair count (copied behind the pair tiles above), then the back end behind the ids
+        // the pair count (copied behind the pair tiles in read_batch_counts), then the back end behind the ids
         BSC_HIP(hipStreamSynchronize(s));
         x->hscal[DS_B_NPAIR] = x->hscal[DS_COUNT];
         BSC_HIP(hipStreamWaitEvent(s, x->ev_ids, 0));
         BSC_TRY(dense_reduce_batch(x, tokens, token_dtype, n_frames));
-    } else if (side_order && !exact) {
-        BSC_TRY(dense_reduce_batch(x, tokens, token_dtype, n_frames));
     }
-    if (side_order && exact) BSC_HIP(hipStreamWaitEvent(s, x->ev_runs, 0));       // k_append reads the pass list k_runs wrote
+    if (c.sched == SCHED_SIDE) BSC_HIP(hipStreamWaitEvent(s, x->ev_runs, 0));       // k_append reads the pass list k_pass_list wrote
     // rgb chain + top-down map: sequential-latency bound, on the library's side stream — and DEFERRED: the
     // call only marks its point order ready; the kernels are launched at the start of the next bsc_ingest (or by whatever
     // needs their result first: exports, merges, resets — sync_all).  The chain's long tail (one voxel seen in every frame
@@ -2080,43 +2147,17 @@ bsc_status ingest_batch(bsc_ctx *x, int32_t n_frames, const float *depth, const 
     // caller's encoder: its few resident wavefronts are harmless beside streaming kernels, but a library GEMM that splits
     // its work statically over all 256 CUs (stream-K) runs up to twice as long while any CU is held by a chain wavefront
     // (measured: 26.4 -> 22.3 ms per 384-frame step without the chain beside the encoder).
-    BSC_HIP(hipEventRecord(x->ev_ready[set], so));
-    x->last_order_set = side_order ? set : -1;
-    x->chain_pending = true;
-    x->chain_set = set;
-    x->chain_order_base = x->order_base;
-    x->chain_points = P;
+    BSC_HIP(hipEventRecord(c.S->ev_ready, so));
+    x->last_order_set = c.sched != SCHED_MAIN ? set : -1;
+    x->chain.pending = true;
+    x->chain.set = set;
+    x->chain.order_base = x->order_base;
+    x->chain.points = P;
     stat_end(x, BSC_STAT_INGEST, 0.0);
     BSC_HIP(hipGetLastError());
     x->order_base += P;
     static const bool chain_eager = getenv("BSC_CHAIN_EAGER") != nullptr;
     if (chain_eager) BSC_TRY(launch_pending_chain(x));      // A/B: the chain right behind its order stage instead of at the next call
-    if (x->c.mode == BSC_MODE_EXACT) {
-        // memory_2.py:880-886: rows fill the cache in order; the point that finds it full triggers the
-        // flush (:881, the policy of bsc_set_flush_policy) and loses its own token.
-        int64_t remaining = x->hscal[DS_B_NPASS], q = 0;
-        while (remaining > 0) {
-            const int64_t room = x->c.iter_size - x->iter_id;
-            const int64_t n = remaining < room ? remaining : room;
-            if (n > 0) {
-                const dim3 agrid((unsigned)((n * 64 + TPB - 1) / TPB));
-                if (token_dtype == BSC_TOK_BF16)
-                    hipLaunchKernelGGL(k_append<bf16_t>, agrid, block, 0, s, x->pass_list, q, n, x->iter_id, x->p_cell,
-                                       x->p_patf, x->p_r2f, (const bf16_t *)tokens, x->g2, x->c.token_dim, x->c.grid_size,
-                                       x->nh, x->cache_f, x->cache_pos, x->cache_d);
-                else
-                    hipLaunchKernelGGL(k_append<float>, agrid, block, 0, s, x->pass_list, q, n, x->iter_id, x->p_cell,
-                                       x->p_patf, x->p_r2f, (const float *)tokens, x->g2, x->c.token_dim, x->c.grid_size,
-                                       x->nh, x->cache_f, x->cache_pos, x->cache_d);
-                BSC_HIP(hipGetLastError());
-                x->iter_id += n; q += n; remaining -= n;
-            }
-            if (remaining > 0) {        // next passing point meets a full cache
-                if (x->flush_policy == BSC_FLUSH_SURPRISE) BSC_TRY(surprise_flush(x, x->fp_radius, x->fp_sthr, x->fp_bthr));
-                else BSC_TRY(flush_cache(x, draw, user));
-                q += 1; remaining -= 1;
-            }
-        }
-    }
+    if (c.exact) BSC_TRY(append_exact(x, tokens, token_dtype, draw, user));
     return BSC_OK;
 }

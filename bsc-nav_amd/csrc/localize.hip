@@ -571,7 +571,7 @@ static bsc_status ensure_name_ranks(bsc_ctx *x, const VoxelView &v)
     const int n_cand = v.max_id + 1;
     const dim3 block(TPB), cgrid((n_cand + TPB - 1) / TPB);
     hipLaunchKernelGGL(k_name_keys, cgrid, block, 0, x->stream, n_cand, v.max_id, v.vcap, v.rgb_pos, v.cnt, x->l_key_a, x->l_val_a);
-    BSC_TRY(prim_sort_pairs(x, x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b, (size_t)n_cand, 0, 64));
+    BSC_TRY(prim_sort_pairs(lane_main(x), x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b, (size_t)n_cand, 0, 64));
     hipLaunchKernelGGL(k_name_rank, cgrid, block, 0, x->stream, n_cand, x->l_val_b, x->l_name_rank);
     x->names_dirty = false;
     return BSC_OK;
@@ -635,7 +635,7 @@ static bsc_status select_and_copy_out(bsc_ctx *x, const A &ca, int nq, int K, in
     } else {                                   // large K: device-wide sort per query
         for (int qi = 0; qi < nq; ++qi) {
             hipLaunchKernelGGL(k_candidates<A>, cgrid, block, 0, s, ca, qi, x->l_sims + (int64_t)qi * sstride, x->l_key_a, x->l_val_a);
-            BSC_TRY(prim_sort_pairs(x, x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b, (size_t)ca.n_cand, 0, 64));
+            BSC_TRY(prim_sort_pairs(lane_main(x), x->l_key_a, x->l_key_b, x->l_val_a, x->l_val_b, (size_t)ca.n_cand, 0, 64));
             hipLaunchKernelGGL(k_gather_topk, dim3((K + TPB - 1) / TPB), block, 0, s, K, ca.n_cand, ca.max_id, ca.vcap, x->l_key_b,
                                x->l_val_b, (int64_t)0, x->rgb_pos, x->l_out_pos + (int64_t)qi * K * 3,
                                x->l_out_sim + (int64_t)qi * K);
@@ -846,7 +846,7 @@ bsc_status region_scan(bsc_ctx *x, const float *q_dev, int32_t nq, const bsc_reg
         hipLaunchKernelGGL(k_region_visibility, dim3(nblk), block, 0, s, n_cand, v.max_id, v.vcap, v.exact, v.rgb_pos, v.cnt,
                            (const RegionDev *)w->regions, nq, w->mask, mask_stride, w->vis, w->blk_tot);
         if (!never) {
-            BSC_TRY(prim_exclusive_sum_i64(x, w->blk_tot, w->blk_off, (size_t)nblk + 1));
+            BSC_TRY(prim_exclusive_sum_i64(lane_main(x), w->blk_tot, w->blk_off, (size_t)nblk + 1));
             BSC_HIP(hipMemcpyAsync(w->tot_pin, w->blk_off + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, s));
             BSC_HIP(hipStreamSynchronize(s));
             n_vis = *w->tot_pin >> RG_ROWS_BITS;

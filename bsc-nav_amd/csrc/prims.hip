@@ -43,7 +43,7 @@ size_t prim_workspace_bytes(size_t n)
 
 #define PRIM_CALL(call)                                             \
     do {                                                            \
-        size_t bytes = x->prim_tmp_bytes;                           \
+        size_t bytes = l.tmp_bytes;                                 \
         hipError_t e = (call);                                      \
         if (e != hipSuccess) {                                      \
             bsc_set_error("rocprim: %s", hipGetErrorString(e));     \
@@ -51,63 +51,63 @@ size_t prim_workspace_bytes(size_t n)
         }                                                           \
     } while (0)
 
-bsc_status prim_sort_keys(bsc_ctx *x, const u64 *in, u64 *out, size_t n, int b0, int b1)
+bsc_status prim_sort_keys(const PrimLane &l, const u64 *in, u64 *out, size_t n, int b0, int b1)
 {
     if (n == 0) return BSC_OK;
-    PRIM_CALL(rocprim::radix_sort_keys(x->prim_tmp, bytes, in, out, n, b0, b1, x->stream));
+    PRIM_CALL(rocprim::radix_sort_keys(l.tmp, bytes, in, out, n, b0, b1, l.stream));
     return BSC_OK;
 }
 
-bsc_status prim_sort_pairs(bsc_ctx *x, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, size_t n, int b0,
+bsc_status prim_sort_pairs(const PrimLane &l, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, size_t n, int b0,
                            int b1)
 {
     if (n == 0) return BSC_OK;
-    PRIM_CALL(rocprim::radix_sort_pairs(x->prim_tmp, bytes, kin, kout, vin, vout, n, b0, b1, x->stream));
+    PRIM_CALL(rocprim::radix_sort_pairs(l.tmp, bytes, kin, kout, vin, vout, n, b0, b1, l.stream));
     return BSC_OK;
 }
 
-bsc_status prim_sort_pairs_onesweep(bsc_ctx *x, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, size_t n,
+bsc_status prim_sort_pairs_onesweep(const PrimLane &l, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, size_t n,
                                     int b0, int b1)
 {
     if (n == 0) return BSC_OK;
-    PRIM_CALL(rocprim::radix_sort_pairs<onesweep_always>(x->prim_tmp, bytes, kin, kout, vin, vout, n, b0, b1, x->stream));
+    PRIM_CALL(rocprim::radix_sort_pairs<onesweep_always>(l.tmp, bytes, kin, kout, vin, vout, n, b0, b1, l.stream));
     return BSC_OK;
 }
 
-bsc_status prim_sort_pairs_u32(bsc_ctx *x, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
+bsc_status prim_sort_pairs_u32(const PrimLane &l, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
                                size_t n, int b0, int b1)
 {
     if (n == 0) return BSC_OK;
-    PRIM_CALL(rocprim::radix_sort_pairs(x->prim_tmp, bytes, kin, kout, vin, vout, n, b0, b1, x->stream));
+    PRIM_CALL(rocprim::radix_sort_pairs(l.tmp, bytes, kin, kout, vin, vout, n, b0, b1, l.stream));
     return BSC_OK;
 }
 
-bsc_status prim_sort_pairs_u32_onesweep(bsc_ctx *x, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
+bsc_status prim_sort_pairs_u32_onesweep(const PrimLane &l, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
                                         size_t n, int b0, int b1)
 {
     if (n == 0) return BSC_OK;
-    PRIM_CALL(rocprim::radix_sort_pairs<onesweep_always>(x->prim_tmp, bytes, kin, kout, vin, vout, n, b0, b1, x->stream));
+    PRIM_CALL(rocprim::radix_sort_pairs<onesweep_always>(l.tmp, bytes, kin, kout, vin, vout, n, b0, b1, l.stream));
     return BSC_OK;
 }
 
-bsc_status prim_exclusive_sum_i64(bsc_ctx *x, const int64_t *in, int64_t *out, size_t n)
+bsc_status prim_exclusive_sum_i64(const PrimLane &l, const int64_t *in, int64_t *out, size_t n)
 {
     if (n == 0) return BSC_OK;
-    PRIM_CALL(rocprim::exclusive_scan(x->prim_tmp, bytes, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), x->stream));
+    PRIM_CALL(rocprim::exclusive_scan(l.tmp, bytes, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), l.stream));
     return BSC_OK;
 }
 
-bsc_status prim_exclusive_sum_i32(bsc_ctx *x, const int32_t *in, int32_t *out, size_t n)
+bsc_status prim_exclusive_sum_i32(const PrimLane &l, const int32_t *in, int32_t *out, size_t n)
 {
     if (n == 0) return BSC_OK;
-    PRIM_CALL(rocprim::exclusive_scan(x->prim_tmp, bytes, in, out, (int32_t)0, n, rocprim::plus<int32_t>(), x->stream));
+    PRIM_CALL(rocprim::exclusive_scan(l.tmp, bytes, in, out, (int32_t)0, n, rocprim::plus<int32_t>(), l.stream));
     return BSC_OK;
 }
 
-bsc_status prim_inclusive_max_i32(bsc_ctx *x, const int32_t *in, int32_t *out, size_t n)
+bsc_status prim_inclusive_max_i32(const PrimLane &l, const int32_t *in, int32_t *out, size_t n)
 {
     if (n == 0) return BSC_OK;
-    PRIM_CALL(rocprim::inclusive_scan(x->prim_tmp, bytes, in, out, n, max_i32(), x->stream));
+    PRIM_CALL(rocprim::inclusive_scan(l.tmp, bytes, in, out, n, max_i32(), l.stream));
     return BSC_OK;
 }
 

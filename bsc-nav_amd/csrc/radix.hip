@@ -272,9 +272,11 @@ __global__ __launch_bounds__(RX_THREADS) void k_radix_pass(const uint32_t *__res
     }
 }
 
-bsc_status radix_sort_pairs_u32(bsc_ctx *x, RadixWs *ws, hipStream_t st, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
-                                uint32_t *vout, size_t n, int b0, int b1)
+bsc_status radix_sort_pairs_u32(const PrimLane &l, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n,
+                                int b0, int b1)
 {
+    RadixWs *const ws = l.rx;
+    const hipStream_t st = l.stream;
     if (n == 0) return BSC_OK;
     const int nbits = b1 - b0;
     if (nbits <= 0) {

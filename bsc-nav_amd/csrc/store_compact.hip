@@ -139,7 +139,7 @@ bsc_status compact_store_impl(bsc_ctx *x, int64_t live_known, int64_t *rows_befo
         BSC_HIP(hipMemsetAsync(w.blk_tot + nblk, 0, sizeof(int64_t), s));       // the scan's last output is the total
         hipLaunchKernelGGL(k_compact_mark, sgrid, block, 0, s, n_slots, cs, x->store_cnt, x->store_rows, pool_n, w.mark);
         hipLaunchKernelGGL(k_compact_count, rgrid, block, 0, s, pool_n, L, (const uint8_t *)w.mark, w.blk_tot);
-        BSC_TRY(prim_exclusive_sum_i64(x, w.blk_tot, w.blk_off, (size_t)nblk + 1));
+        BSC_TRY(prim_exclusive_sum_i64(lane_main(x), w.blk_tot, w.blk_off, (size_t)nblk + 1));
         int64_t tot = 0;
         BSC_HIP(hipGetLastError());
         BSC_HIP(hipMemcpyAsync(&tot, w.blk_off + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, s));

@@ -656,11 +656,11 @@ bsc_status surprise_flush(bsc_ctx *x, int32_t radius, double sthr, double bthr)
     const dim3 block(TPB), grid((n + TPB - 1) / TPB), wgrid((unsigned)(((int64_t)n * 64 + TPB - 1) / TPB));
     hipLaunchKernelGGL(k_surp_rows, grid, block, 0, s, n, x->cache_pos, x->occ, x->c.grid_size, x->nh, vcap, ws->ent, ws->head);
     hipLaunchKernelGGL(k_surp_rowinv, wgrid, block, 0, s, n, x->cache_f, D, ws->inv);
-    BSC_TRY(prim_exclusive_sum_i32(x, ws->head, ws->tid, (size_t)n));
+    BSC_TRY(prim_exclusive_sum_i32(lane_main(x), ws->head, ws->tid, (size_t)n));
     BSC_HIP(hipMemsetAsync(ws->cid, 0x7f, sizeof(int32_t) * ((size_t)vcap + 1), s));
     hipLaunchKernelGGL(k_surp_tasks, grid, block, 0, s, n, ws->ent, ws->head, ws->tid, ws->tstart, ws->tent, ws->cid, ws->scal);
     hipLaunchKernelGGL(k_surp_first, grid, block, 0, s, n, ws->ent, ws->head, ws->tid, ws->cid, ws->first);
-    BSC_TRY(prim_exclusive_sum_i32(x, ws->first, ws->dense, (size_t)n));
+    BSC_TRY(prim_exclusive_sum_i32(lane_main(x), ws->first, ws->dense, (size_t)n));
     hipLaunchKernelGGL(k_surp_dense, grid, block, 0, s, n, ws->ent, ws->first, ws->dense, ws->cid, ws->scal);
     int32_t hs[3] = {0, 0, 0};
     BSC_HIP(hipMemcpyAsync(hs, ws->scal, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, s));

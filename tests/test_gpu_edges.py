@@ -429,6 +429,56 @@ def test_chain_and_order_knobs_keep_the_result(knob):
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
+def _exact_two_calls(out_path):
+    """Exact mode, every pixel: 4 frames of 240x320 as 2 calls of 2 into a 64-cell grid (D = 8, g = 14).  The token cache holds as
+    many rows as a call has points, so no flush can happen in the first call and the one the counters report happened INSIDE the
+    second.  Everything a schedule could change goes to out_path: token store, rgb state, top-down map."""
+    import random
+    import torch
+    import bsc_nav_amd as B
+    import synth
+    H, W, g, D, gs, F = 240, 320, 14, 8, 64, 4
+    rgb, depth, poses = synth.make_frames(33, F, H, W, "room")
+    tokens = synth.make_tokens(33, F, g, D)
+    eng = B.VoxelEngine(H, W, gs, 0.25, -2.0, 4.4, g, D, mode="exact", iter_size=2 * H * W, voxel_capacity=60_000,
+                        token_capacity=700_000, max_points=2 * H * W)
+    chain = B.PoseChain()
+    Ts = np.stack([chain.pc_transform(p) for p in poses])
+    random.seed(12)                                      # the replacement draws of the flush
+    d_depth, d_rgb, d_tok = (torch.from_numpy(a).cuda() for a in (depth, rgb, tokens))
+    for a in range(0, F, 2):
+        eng.ingest(d_depth[a:a + 2], d_rgb[a:a + 2], d_tok[a:a + 2], Ts[a:a + 2])
+    k = eng.counters()
+    print("counters", k)
+    assert k["flushes"] == 1 and k["points_passed"] > 2 * H * W + 1 and k["max_id"] > 1000, k
+    eng.flush()
+    arrays = [*eng.export_store(), *eng.export_rgb(), *eng.export_heightmap()]
+    assert arrays[1].max() == 10                         # saturated voxels: the in-call flush replaced rows
+    np.savez(out_path, *arrays)
+    eng.close()
+
+
+def test_exact_mode_on_the_main_stream_keeps_the_result(tmp_path):
+    """BSC_ORDER_MAIN=1 in exact mode (order stage, ids and k_append all on the main stream: the one schedule of ingest_batch the
+    knob test, whose scene is dense, does not reach), with a flush inside the second call: token store, rgb state and top-down
+    map bit for bit those of the default schedule.  The switch is read once per process: each run in its own interpreter."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = {}
+    for label, extra in (("side", {}), ("main", {"BSC_ORDER_MAIN": "1"})):
+        out = str(tmp_path / (label + ".npz"))
+        code = ("import sys; sys.path[:0] = ['.', 'tests', 'tests/golden']; import test_gpu_edges as t; "
+                "t._exact_two_calls(%r); print('ok')" % out)
+        env = {k: v for k, v in os.environ.items() if k != "BSC_ORDER_MAIN"}
+        r = subprocess.run([sys.executable, "-c", code], env=dict(env, **extra), cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+        with np.load(out) as z:
+            got[label] = [z[n] for n in z.files]
+    assert len(got["side"]) == len(got["main"]) == 9
+    for a, b in zip(got["side"], got["main"]):
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+
+
 def test_weight_ties_and_saturation_against_oracle():
     """A handful of 50 m cells take every point.  alpha = 1 until the f32 weights pass 2^23 (one ulp = 1), then values
     from {0.25, 0.5, 0.75, 1}: 0.5 is an exact tie whose rounding depends on the parity of the running weight (the
