@@ -18,13 +18,14 @@
 //   A operand  straight from global memory in fragment layout — lane (i = lane & 31, g = lane >> 5) loads the 16 floats
 //              [32 c + 16 g, + 16) of its row (one 128-byte line per row and K chunk over the two lane groups) and splits
 //              them in registers (v_cvt_pk_f16_f32);
-//   W operand  pieces precomputed once per weight matrix (bsc_enc_split_weights: planes h, l of (N,K) fp16), staged per 32-wide
-//              K chunk through LDS (80-byte row pitch: conflict-free 16-byte reads), double-buffered;
+//   W operand  pieces precomputed once per weight matrix (bsc_enc_split_weights: planes h, l of (N,K) fp16), one 32-wide K chunk
+//              at a time from global memory straight into LDS (global_load_lds_dwordx4: no register stage), double-buffered;
+//              64-byte rows whose 16-byte columns are XOR-swizzled on the SOURCE address (conflict-free 16-byte reads);
 //   MFMA       the weights are the FIRST operand (D' = W X^T), so a lane of the accumulator tile holds ONE row of C and four
 //              consecutive columns per register quad;
 //   epilogue   bias, bias + GELU(tanh), bias + residual (C may alias the residual) — nothing elementwise is left between GEMMs.
 //              Each wavefront turns its 32 x 32 tiles round in 4 KB of LDS of its own and moves them as whole 128-byte lines
-//              (f32 rows or piece chunks), the residual rows requested three tiles ahead.
+//              (f32 rows or piece chunks), the residual rows requested right before the tile that adds them.
 // Workgroup ids map so that the workgroups of an XCD (id mod 8) walk the column tiles of ONE row tile back to back: the 786 KB
 // A tile is fetched into that XCD's L2 once.
 #include "bsc_internal.h"
@@ -36,15 +37,22 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 #define GS_KC 32                 // K chunk
-#define GS_PITCH 40              // fp16 elements per staged weight row (80 bytes)
+#define GS_PITCH 40              // fp16 elements per weight row staged through registers (80 bytes: the few-rows tile, or BSC_GEMM_W_DMA=0)
 #define GS_TPB 256
 #ifndef GS_RESID_DEPTH
 #define GS_RESID_DEPTH 1             // tiles of residual rows in flight in the epilogue (incl. the one in use).  Round 5 sweep at 768 frames
                                      // (proj / fc2, us): depth 3 736 / 2466, 2 719 / 2405, 1 679 / 2328 — the registers of the prefetched rows
-                                     // (16 per tile in flight) are worth more to the main loop than the prefetch is to the epilogue
+                                     // (16 per tile in flight) are worth more to the main loop than the prefetch is to the epilogue.
+                                     // Prefetching ONE tile ahead through LDS instead (global_load_lds into 4 KB per wavefront, no register
+                                     // held across the loop) was measured on top of the weight DMA and dropped: the epilogue of a proj tile
+                                     // went 14.3 -> 12.5 us, the forward at 768 frames 88.6 -> 89.0 ms (profiles/README.md) — one tile of
+                                     // cover is less than the rows' HBM latency, and LDS has no room for a second slot per wavefront.
 #endif
 #ifndef GS_STATS_RESID_DEPTH
 #define GS_STATS_RESID_DEPTH 1       // the same in the epilogue that also takes the row statistics
+#endif
+#ifndef BSC_GEMM_W_DMA
+#define BSC_GEMM_W_DMA 1             // weight chunks global -> LDS without a register stage (0: the register-staged form, for A/B builds)
 #endif
 #ifndef BSC_GEMM_NARROW_TILE
 #define BSC_GEMM_NARROW_TILE 1           // tile variant for N <= 1024 (see bsc_enc_gemm_split)
@@ -76,6 +84,26 @@ __device__ __forceinline__ void gs_wave_lds_order()
 {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront", "local");
     __builtin_amdgcn_wave_barrier();
+}
+
+// LDS-DMA (global_load_lds_dwordx4): every lane names 16 bytes of global memory, the wavefront's 1 KB lands at lds_base + 16 lane
+// (lds_base: wave-uniform LDS byte address, travels in M0) — no register destination.  Issued as inline assembly, so the compiler
+// does not count it: beside a DMA it knows of (__builtin_amdgcn_global_load_lds) it waits for EVERY outstanding load at the next use
+// of an ordinary one and before every barrier, which would cost the A operand its two chunks of prefetch.  The caller waits with
+// gs_wait_vm<N>() (N = vector memory operations issued after the DMA that may stay in flight; the counter retires in issue order),
+// then passes a barrier, before any wavefront reads the bytes.  An operation the compiler does not count can only make its own
+// counted waits stricter, never too weak: a wait for "all but the n youngest" covers whatever is older than those n.
+// The source address is a uniform base + a 32-bit byte offset per lane: one address register per lane however many pieces.
+__device__ __forceinline__ void gs_dma16(const void *sbase, uint32_t voff, uint32_t lds_base)
+{
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_base) : "memory");
+}
+template <int N> __device__ __forceinline__ void gs_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ uint32_t gs_lds_addr(const void *p)        // LDS byte address of a pointer into LDS, as a scalar
+{
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)p);
 }
 
 // (a, b) -> packed fp16 pieces h, l of both
@@ -323,12 +351,16 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // k_full: the operands' row length (A rows, weight rows); K: the stretch of it this launch contracts (split-K slices of the
     // few-rows path: the kernel wrapper has moved the operand pointers to the slice's first column; otherwise K == k_full)
     constexpr bool APIECES = AMODE == GS_A_PIECES;
-    constexpr int WROWS = WC * NT * 32;                                       // Ws: [2][2][WROWS][GS_PITCH]
+    constexpr bool DEEP = MR == 1 && NT == 1 && WR == 1;                      // the few-rows tile (below): keeps the register-staged weights
+    constexpr bool WDMA = BSC_GEMM_W_DMA && !DEEP;
+    constexpr int PITCH = WDMA ? GS_KC : GS_PITCH;                            // a DMA's LDS image is lane-linear: no padding
+    constexpr int WROWS = WC * NT * 32;                                       // Ws: [2][2][WROWS][PITCH]
     constexpr int TROWS = WR * MR * 32;
-    constexpr int BUF = 2 * WROWS * GS_PITCH;
+    constexpr int BUF = 2 * WROWS * PITCH;
     constexpr int NTHR = 64 * WR * WC;
     constexpr int NLD = 2 * WROWS * 4 / NTHR;                                 // 16-byte pieces of a weight chunk per thread
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // (the wavefront's index as a scalar: its rows, LDS blocks and strips are then scalar arithmetic, not registers per lane)
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = w / WC, wc = w - wr * WC;
     const int i = lane & 31, g = lane >> 5;
 #ifdef BSC_GEMM_PROFILE
@@ -400,8 +432,22 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // (buffer loads: a 32-bit per-thread offset + a scalar offset.  With 64-bit pointers the compiler kept one loop-invariant
     // pointer per j in registers — and, in the persistent form of this kernel, in scratch.)
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void *)Wp, 0, (int)(4 * w_plane), 0x00020000);
-    const int wthr = ((tid >> 2) * k_full + (tid & 3) * 8) * 2;
+    // DMA form: a wavefront's instruction moves 16 rows x 64 bytes, which land in lane order — LDS slot (row, c'), c' the 16-byte
+    // column, holds global column c' ^ ((row >> 2) & 3) (the swizzle is on the source address; PR is a multiple of 16, so it is the
+    // same for every j).  The fragment reads below apply the same XOR: 16 consecutive lanes read rows r .. r + 15 at column cc, i.e.
+    // the 16-byte bank slots 4 (row & 3) + (cc ^ (row >> 2 & 3)) — 16 different ones of the 16.
+    const int wthr = ((tid >> 2) * k_full + (WDMA ? (tid & 3) ^ ((tid >> 4) & 3) : tid & 3) * 8) * 2;
     const int lthr = (tid >> 2) * GS_PITCH + (tid & 3) * 8;
+    const uint32_t ws_m0 = gs_lds_addr((const char *)Ws + w * 1024);        // where the wavefront's 16 rows of piece j = 0 land
+    auto dma_w = [&](int buf, int nbase, int c) {
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            // (the uniform part of the address fits 32 bits — the planes of one matrix — and is made a scalar by hand)
+            const int uni = (int)(((int64_t)(j / PPP) * w_plane + (int64_t)(nbase + (j % PPP) * PR) * k_full + c * GS_KC) * 2);
+            gs_dma16((const char *)Wp + (uint32_t)__builtin_amdgcn_readfirstlane(uni), (uint32_t)wthr, ws_m0 + (uint32_t)(buf * BUF + ((j / PPP) * WROWS + (j % PPP) * PR) * PITCH) * 2);
+        }
+    };
+    // the register-staged form (the few-rows tile; BSC_GEMM_W_DMA=0): global -> registers (load_w), registers -> LDS a chunk later (store_w)
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     auto load_w = [&](qr_t &q, int nbase, int c) {
 #pragma unroll
@@ -420,14 +466,15 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // so the weight chunks travel TWO iterations ahead in two register sets that alternate (chunk c + 2 is requested in iteration
     // c, chunk c + 1 — requested an iteration earlier — is stored to LDS at its end): the loop turns on LDS + barrier time instead of
     // one L2 round trip per chunk.  Such tiles do not chain (every tile has its prologue).
-    constexpr bool DEEP = MR == 1 && NT == 1 && WR == 1;
     qr_t qr2;
     if (!primed) {
+        if (WDMA) dma_w(par, n0, 0);
         load_a(xf, arow, 0);
-        load_w(qr, n0, 0);
+        if (!WDMA) load_w(qr, n0, 0);
         if (nchunks > 1) load_a(xg, arow, 1);
         if (DEEP && nchunks > 1) load_w(qr2, n0, 1);
-        store_w(qr, par);
+        if (WDMA) gs_wait_vm<0>();
+        else store_w(qr, par);
         __syncthreads();
     }
     GS_T(2);
@@ -467,6 +514,10 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
         // ONE load site per operand: the last two chunks request the next tile's first two (a second load site under its own
         // branch made the compiler merge the two results with register copies — and wait for the loads right there)
         const bool a_next = c + 2 >= nchunks, w_next = c + 1 >= nchunks;
+        // Issue order of a chunk: the next weight chunk's DMA, then the A loads.  The wait at the chunk's end then leaves exactly the
+        // A loads in flight, and the DMAs — older than those — add nothing to the compiler's own count for them.
+        const bool w_req = !w_next || has_next, a_req = DEEP || !a_next || has_next;
+        if (WDMA && w_req) dma_w(buf ^ 1, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
         if (DEEP) {
             // unconditional requests (the last two iterations repeat the last chunk): behind a branch the compiler cannot count on the
             // younger loads being in flight and makes the LDS stores below wait for everything
@@ -478,21 +529,24 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
             load_a(xg, ap, a_next ? c + 2 - nchunks : c + 2);
         }
         if (DEEP) load_w(q_load, n0, a_next ? nchunks - 1 : c + 2);
-        else if (!w_next || has_next) load_w(q_load, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
-        const uint16_t *wb = &Ws[buf * BUF + (wc * NT * 32 + i) * GS_PITCH + g * 16];
+        else if (!WDMA && w_req) load_w(q_load, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
+        // the lane's 16-byte column of sub-step sstep is 2 g + sstep; swizzled rows hold it at (2 g + sstep) ^ ((row >> 2) & 3)
+        const uint16_t *wrow = &Ws[buf * BUF + (wc * NT * 32 + i) * PITCH];
+        const uint16_t *wbs[2] = {wrow + (WDMA ? ((2 * g) ^ ((i >> 2) & 3)) * 8 : g * 16), wrow + (WDMA ? ((2 * g + 1) ^ ((i >> 2) & 3)) * 8 : g * 16 + 8)};
 #pragma unroll
         for (int sstep = 0; sstep < 2; ++sstep) {
             // one piece of the weights at a time; smallest terms first; consecutive MFMAs go to different accumulators
+            const uint16_t *wb = wbs[sstep];
             half8_t wf[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) wf[t] = *(const half8_t *)(wb + (1 * WROWS + t * 32) * GS_PITCH + sstep * 8);
+            for (int t = 0; t < NT; ++t) wf[t] = *(const half8_t *)(wb + (1 * WROWS + t * 32) * PITCH);
 #pragma unroll
             for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
                     acc[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)ah[mr][sstep], acc[mr][t], 0, 0, 0);     // h l
 #pragma unroll
-            for (int t = 0; t < NT; ++t) wf[t] = *(const half8_t *)(wb + (0 * WROWS + t * 32) * GS_PITCH + sstep * 8);
+            for (int t = 0; t < NT; ++t) wf[t] = *(const half8_t *)(wb + (0 * WROWS + t * 32) * PITCH);
 #pragma unroll
             for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -504,7 +558,11 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                 for (int t = 0; t < NT; ++t)
                     acc[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)ah[mr][sstep], acc[mr][t], 0, 0, 0);     // h h
         }
-        if (c + 1 < nchunks || (!DEEP && has_next)) store_w(q_store, buf ^ 1);
+        if (WDMA) {
+            // the DMAs have landed before any wavefront reads the buffer (after the barrier); the A loads stay in flight
+            if (a_req) gs_wait_vm<4 * MR>();
+            else gs_wait_vm<0>();
+        } else if (c + 1 < nchunks || (!DEEP && has_next)) store_w(q_store, buf ^ 1);
         __syncthreads();
     };
     if (DEEP) {
@@ -1085,7 +1143,7 @@ extern "C" bsc_status bsc_enc_gemm_split_ws(const void *a_dev, int64_t M, int32_
     const int64_t q_full = (tile == 1 && tail_env && q_rem > 0 && 2 * q_rem <= per_round && q_all > per_round) ? q_all - q_rem : q_all;
     const int64_t q_virtual = q_full + 2 * (q_all - q_full);
     const int64_t n_wg = (q_virtual < per_round ? q_virtual : per_round) * 8;     // persistent: one workgroup per CU
-    const size_t lds_loop = (size_t)2 * 2 * TCOLS * GS_PITCH * sizeof(uint16_t);
+    const size_t lds_loop = (size_t)2 * 2 * TCOLS * ((BSC_GEMM_W_DMA && tile != 6) ? GS_KC : GS_PITCH) * sizeof(uint16_t);
     const size_t lds_epi = (size_t)(NTHR / 64) * (32 * 136);                      // the epilogue's per-wavefront tile blocks
     const size_t lds = lds_loop + lds_epi + (size_t)n_pad * sizeof(float);        // + the bias row
     if (lds > 160 * 1024) { bsc_set_error("bsc_enc_gemm_split: N = %d does not fit the kernel's LDS plan (bias row)", N); return BSC_E_INVALID; }
