@@ -270,6 +270,17 @@ struct bsc_ctx {
         if (_s != BSC_OK) return _s;  \
     } while (0)
 
+// current device ordinal and its CU count (cached per ordinal; kernel attributes and the persistent grids are per device)
+inline bsc_status gs_device(int *dev, int *n_cu)
+{
+    static int cus[64] = {0};
+    BSC_HIP(hipGetDevice(dev));
+    int &c = cus[*dev & 63];
+    if (!c) BSC_HIP(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, *dev));
+    *n_cu = c;
+    return BSC_OK;
+}
+
 // sum of v over the wavefront's 64 lanes, in every lane (xor butterfly, distances 32 .. 1)
 __device__ __forceinline__ float wave_sum(float v)
 {

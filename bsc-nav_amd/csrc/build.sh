@@ -17,7 +17,7 @@ objs=()
 for f in $SOURCES; do
   src="$HERE/$f"; obj="$OBJ/${f%.*}.o"
   objs+=("$obj")
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/bsc_internal.h" -nt "$obj" ] || [ "$HERE/ctx_mem.h" -nt "$obj" ] || [ "$HERE/ingest_mail.h" -nt "$obj" ] || [ "$HERE/localize_cand.h" -nt "$obj" ] || [ "$HERE/geometry_dev.h" -nt "$obj" ] || [ "$HERE/../../include/bscnav.h" -nt "$obj" ]; then
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/bsc_internal.h" -nt "$obj" ] || [ "$HERE/ctx_mem.h" -nt "$obj" ] || [ "$HERE/ingest_mail.h" -nt "$obj" ] || [ "$HERE/localize_cand.h" -nt "$obj" ] || [ "$HERE/att_ticket.h" -nt "$obj" ] || [ "$HERE/gemm_split_plan.h" -nt "$obj" ] || [ "$HERE/geometry_dev.h" -nt "$obj" ] || [ "$HERE/../../include/bscnav.h" -nt "$obj" ]; then
     case "$f" in
       *.cpp) ( g++ -O3 -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I"$ROCM/include" -I"$HERE/../../include" -c "$src" -o "$obj" ) & ;;
       *) ( hipcc $FLAGS -c "$src" -o "$obj" ) & ;;

@@ -29,6 +29,8 @@
 // Workgroup ids map so that the workgroups of an XCD (id mod 8) walk the column tiles of ONE row tile back to back: the 786 KB
 // A tile is fetched into that XCD's L2 once.
 #include "bsc_internal.h"
+#include "att_ticket.h"
+#include "gemm_split_plan.h"          // GS_KC, GS_PITCH, the epilogue / operand mode ids, the launch plan and gs_tile_of
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
@@ -36,29 +38,8 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-#define GS_KC 32                 // K chunk
-#define GS_PITCH 40              // fp16 elements per weight row staged through registers (80 bytes: the few-rows tile, or BSC_GEMM_W_DMA=0)
 #define GS_TPB 256
-#ifndef GS_RESID_DEPTH
-#define GS_RESID_DEPTH 1             // tiles of residual rows in flight in the epilogue (incl. the one in use).  Round 5 sweep at 768 frames
-                                     // (proj / fc2, us): depth 3 736 / 2466, 2 719 / 2405, 1 679 / 2328 — the registers of the prefetched rows
-                                     // (16 per tile in flight) are worth more to the main loop than the prefetch is to the epilogue.
-                                     // Prefetching ONE tile ahead through LDS instead (global_load_lds into 4 KB per wavefront, no register
-                                     // held across the loop) was measured on top of the weight DMA and dropped: the epilogue of a proj tile
-                                     // went 14.3 -> 12.5 us, the forward at 768 frames 88.6 -> 89.0 ms (profiles/README.md) — one tile of
-                                     // cover is less than the rows' HBM latency, and LDS has no room for a second slot per wavefront.
-#endif
-#ifndef GS_STATS_RESID_DEPTH
-#define GS_STATS_RESID_DEPTH 1       // the same in the epilogue that also takes the row statistics
-#endif
-#ifndef BSC_GEMM_W_DMA
-#define BSC_GEMM_W_DMA 1             // weight chunks global -> LDS without a register stage (0: the register-staged form, for A/B builds)
-#endif
-#ifndef BSC_GEMM_NARROW_TILE
-#define BSC_GEMM_NARROW_TILE 1           // tile variant for N <= 1024 (see bsc_enc_gemm_split)
-#endif
 
-enum { GS_EPI_BIAS = 0, GS_EPI_GELU = 1, GS_EPI_RESID = 2, GS_EPI_GELU_ERF = 3 };
 #define GS_LN_REC 20             // floats per LayerNorm statistics record of a residual-stream row (see gemm_split_tile)
 
 #ifdef BSC_GEMM_PROFILE        // per-workgroup phase stamps (100 MHz wall clock) + the CU it ran on: -DBSC_GEMM_PROFILE, BSC_GEMM_PROFILE_DUMP=1
@@ -338,7 +319,6 @@ template <int MR> struct gs_xf { typedef uint32_t type __attribute__((ext_vector
 // tile holds the strip (no atomics); unused slots zero.  mean = s + A / W, var = B / W - (A / W)^2 with A, B the slot sums: the
 // shift is the row's previous mean (ln_mu, written by the GEMM that consumed the previous record), so the one-pass variance is
 // taken about a point within a fraction of a standard deviation of the new mean — as accurate as the two-pass form.
-enum { GS_A_F32 = 0, GS_A_PIECES = 1, GS_A_LN = 2 };
 template <int MR, int NT, int WR, int WC, int EPI, int AMODE, bool CPIECES, bool STATS>
 __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, const float *bias_lds, const void *__restrict__ Av, int64_t M, int K,
                                                 const uint16_t *__restrict__ Wp, int64_t w_plane, int N,
@@ -351,9 +331,10 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // k_full: the operands' row length (A rows, weight rows); K: the stretch of it this launch contracts (split-K slices of the
     // few-rows path: the kernel wrapper has moved the operand pointers to the slice's first column; otherwise K == k_full)
     constexpr bool APIECES = AMODE == GS_A_PIECES;
-    constexpr bool DEEP = MR == 1 && NT == 1 && WR == 1;                      // the few-rows tile (below): keeps the register-staged weights
-    constexpr bool WDMA = BSC_GEMM_W_DMA && !DEEP;
-    constexpr int PITCH = WDMA ? GS_KC : GS_PITCH;                            // a DMA's LDS image is lane-linear: no padding
+    // the two weight schedules: the few-rows tile (DEEP, below) stages its chunks through registers, two chunks ahead; every other
+    // tile moves them global -> LDS by DMA, one chunk ahead
+    constexpr bool DEEP = MR == 1 && NT == 1 && WR == 1;
+    constexpr int PITCH = DEEP ? GS_PITCH : GS_KC;                            // a DMA's LDS image is lane-linear: no padding
     constexpr int WROWS = WC * NT * 32;                                       // Ws: [2][2][WROWS][PITCH]
     constexpr int TROWS = WR * MR * 32;
     constexpr int BUF = 2 * WROWS * PITCH;
@@ -436,7 +417,7 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // column, holds global column c' ^ ((row >> 2) & 3) (the swizzle is on the source address; PR is a multiple of 16, so it is the
     // same for every j).  The fragment reads below apply the same XOR: 16 consecutive lanes read rows r .. r + 15 at column cc, i.e.
     // the 16-byte bank slots 4 (row & 3) + (cc ^ (row >> 2 & 3)) — 16 different ones of the 16.
-    const int wthr = ((tid >> 2) * k_full + (WDMA ? (tid & 3) ^ ((tid >> 4) & 3) : tid & 3) * 8) * 2;
+    const int wthr = ((tid >> 2) * k_full + (DEEP ? tid & 3 : (tid & 3) ^ ((tid >> 4) & 3)) * 8) * 2;
     const int lthr = (tid >> 2) * GS_PITCH + (tid & 3) * 8;
     const uint32_t ws_m0 = gs_lds_addr((const char *)Ws + w * 1024);        // where the wavefront's 16 rows of piece j = 0 land
     auto dma_w = [&](int buf, int nbase, int c) {
@@ -447,7 +428,7 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
             gs_dma16((const char *)Wp + (uint32_t)__builtin_amdgcn_readfirstlane(uni), (uint32_t)wthr, ws_m0 + (uint32_t)(buf * BUF + ((j / PPP) * WROWS + (j % PPP) * PR) * PITCH) * 2);
         }
     };
-    // the register-staged form (the few-rows tile; BSC_GEMM_W_DMA=0): global -> registers (load_w), registers -> LDS a chunk later (store_w)
+    // the register-staged form (the few-rows tile): global -> registers (load_w), registers -> LDS a chunk later (store_w)
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     auto load_w = [&](qr_t &q, int nbase, int c) {
 #pragma unroll
@@ -468,13 +449,17 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // one L2 round trip per chunk.  Such tiles do not chain (every tile has its prologue).
     qr_t qr2;
     if (!primed) {
-        if (WDMA) dma_w(par, n0, 0);
-        load_a(xf, arow, 0);
-        if (!WDMA) load_w(qr, n0, 0);
-        if (nchunks > 1) load_a(xg, arow, 1);
-        if (DEEP && nchunks > 1) load_w(qr2, n0, 1);
-        if (WDMA) gs_wait_vm<0>();
-        else store_w(qr, par);
+        if constexpr (DEEP) {
+            load_a(xf, arow, 0);
+            load_w(qr, n0, 0);
+            if (nchunks > 1) { load_a(xg, arow, 1); load_w(qr2, n0, 1); }
+            store_w(qr, par);
+        } else {
+            dma_w(par, n0, 0);
+            load_a(xf, arow, 0);
+            if (nchunks > 1) load_a(xg, arow, 1);
+            gs_wait_vm<0>();
+        }
         __syncthreads();
     }
     GS_T(2);
@@ -514,25 +499,26 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
         // ONE load site per operand: the last two chunks request the next tile's first two (a second load site under its own
         // branch made the compiler merge the two results with register copies — and wait for the loads right there)
         const bool a_next = c + 2 >= nchunks, w_next = c + 1 >= nchunks;
-        // Issue order of a chunk: the next weight chunk's DMA, then the A loads.  The wait at the chunk's end then leaves exactly the
-        // A loads in flight, and the DMAs — older than those — add nothing to the compiler's own count for them.
-        const bool w_req = !w_next || has_next, a_req = DEEP || !a_next || has_next;
-        if (WDMA && w_req) dma_w(buf ^ 1, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
-        if (DEEP) {
+        const bool w_req = !w_next || has_next, a_req = !a_next || has_next;    // (DMA schedule) whether there is a chunk to request
+        if constexpr (DEEP) {
             // unconditional requests (the last two iterations repeat the last chunk): behind a branch the compiler cannot count on the
             // younger loads being in flight and makes the LDS stores below wait for everything
             load_a(xg, arow, a_next ? nchunks - 1 : c + 2);
-        } else if (!a_next || has_next) {
-            const char *ap[MR];
+            load_w(q_load, n0, a_next ? nchunks - 1 : c + 2);
+        } else {
+            // Issue order of a chunk: the next weight chunk's DMA, then the A loads.  The wait at the chunk's end then leaves exactly the
+            // A loads in flight, and the DMAs — older than those — add nothing to the compiler's own count for them.
+            if (w_req) dma_w(buf ^ 1, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
+            if (a_req) {
+                const char *ap[MR];
 #pragma unroll
-            for (int mr = 0; mr < MR; ++mr) ap[mr] = a_next ? row_base(next_tm * TROWS + wr * (MR * 32), mr) : arow[mr];
-            load_a(xg, ap, a_next ? c + 2 - nchunks : c + 2);
+                for (int mr = 0; mr < MR; ++mr) ap[mr] = a_next ? row_base(next_tm * TROWS + wr * (MR * 32), mr) : arow[mr];
+                load_a(xg, ap, a_next ? c + 2 - nchunks : c + 2);
+            }
         }
-        if (DEEP) load_w(q_load, n0, a_next ? nchunks - 1 : c + 2);
-        else if (!WDMA && w_req) load_w(q_load, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
         // the lane's 16-byte column of sub-step sstep is 2 g + sstep; swizzled rows hold it at (2 g + sstep) ^ ((row >> 2) & 3)
         const uint16_t *wrow = &Ws[buf * BUF + (wc * NT * 32 + i) * PITCH];
-        const uint16_t *wbs[2] = {wrow + (WDMA ? ((2 * g) ^ ((i >> 2) & 3)) * 8 : g * 16), wrow + (WDMA ? ((2 * g + 1) ^ ((i >> 2) & 3)) * 8 : g * 16 + 8)};
+        const uint16_t *wbs[2] = {wrow + (DEEP ? g * 16 : ((2 * g) ^ ((i >> 2) & 3)) * 8), wrow + (DEEP ? g * 16 + 8 : ((2 * g + 1) ^ ((i >> 2) & 3)) * 8)};
 #pragma unroll
         for (int sstep = 0; sstep < 2; ++sstep) {
             // one piece of the weights at a time; smallest terms first; consecutive MFMAs go to different accumulators
@@ -558,11 +544,13 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                 for (int t = 0; t < NT; ++t)
                     acc[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)ah[mr][sstep], acc[mr][t], 0, 0, 0);     // h h
         }
-        if (WDMA) {
+        if constexpr (DEEP) {
+            if (c + 1 < nchunks) store_w(q_store, buf ^ 1);
+        } else {
             // the DMAs have landed before any wavefront reads the buffer (after the barrier); the A loads stay in flight
             if (a_req) gs_wait_vm<4 * MR>();
             else gs_wait_vm<0>();
-        } else if (c + 1 < nchunks || (!DEEP && has_next)) store_w(q_store, buf ^ 1);
+        }
         __syncthreads();
     };
     if (DEEP) {
@@ -588,13 +576,17 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // one 4-byte access per element in accumulator order was 15 us per tile for piece output (VALU: ~25 instructions per element)
     // and 65 us for the residual form (R may alias C, so every load stayed behind the store before it: a memory round trip per
     // element) against 75 us of main loop at K = 768; 16-byte quads straight from the registers were 9 and 34 us (32 lines
-    // touched per instruction: the L1's line rate).  The residual rows are requested RD tiles ahead of their use.
+    // touched per instruction: the L1's line rate).
+    // The residual rows of ONE tile are held (rq), requested right before the tile that adds them.  Round 5 sweep of the tiles in flight
+    // at 768 frames (proj / fc2, us): 3 tiles 736 / 2466, 2 tiles 719 / 2405, 1 tile 679 / 2328 — the 16 registers per prefetched tile
+    // are worth more to the main loop than the prefetch is to the epilogue.  Prefetching one tile ahead through LDS instead (no register
+    // held across the loop) was measured on top of the weight DMA and dropped: a proj tile's epilogue 14.3 -> 12.5 us, the forward at
+    // 768 frames 88.6 -> 89.0 ms (profiles/README.md) — one tile of cover is less than the rows' HBM latency.
     const bool full = row0 + MR * 32 <= M && n0 + WROWS <= N;               // (uniform) no bounds checks inside the tile
     float *C = (float *)Cv;
     uint16_t *Cp = (uint16_t *)Cv;
     constexpr int EP = 136;                                                 // staged row pitch, bytes: conflict-free 8-byte writes
     constexpr int WLB = 32 * EP;                                            // per wavefront: one tile
-    constexpr int RD = STATS ? GS_STATS_RESID_DEPTH : GS_RESID_DEPTH;
     char *wl = epi_lds + w * WLB;                                           // beyond the weight buffers: the next tile's chunk 0 may sit there
     const float *bs = bias_lds + n0 + wc * NT * 32;                         // the bias values of the wavefront's column strip
     const int rl = lane >> 3, seg = lane & 7;                               // line phase: row rl + 8 k of the tile, 16-byte segment seg
@@ -603,22 +595,18 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
         for (int mr = 0; mr < MR; ++mr) {
             const int64_t mbase = row0 + mr * 32;
             if (CPIECES || (N & 3) == 0) {
-                f32x4_t rq[RD][4];
+                f32x4_t rq[4];
                 auto line_ok = [&](int t, int k) {
                     const int n = n0 + (wc * NT + t) * 32 + (CPIECES ? 0 : 4 * seg);
                     return !chk || (mbase + rl + 8 * k < M && n < N);
                 };
-                auto load_r = [&](int slot, int t) {
+                auto load_r = [&](int t) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
-                        rq[slot][k] = line_ok(t, k) ? *(const f32x4_t *)(R + (mbase + rl + 8 * k) * N + n0 + (wc * NT + t) * 32 + 4 * seg) : z;
+                        rq[k] = line_ok(t, k) ? *(const f32x4_t *)(R + (mbase + rl + 8 * k) * N + n0 + (wc * NT + t) * 32 + 4 * seg) : z;
                     }
                 };
-                if (EPI == GS_EPI_RESID) {
-#pragma unroll
-                    for (int t = 0; t < RD - 1 && t < NT; ++t) load_r(t, t);
-                }
                 // statistics of the finished rows for the next LayerNorm: shifted sums per 128-column strip (the line phase below
                 // holds row rl + 8 k of the tile, four columns per lane: eight lanes per row)
                 float st_s[4], st_a[4], st_b[4];
@@ -633,7 +621,7 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                 }
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
-                    if (EPI == GS_EPI_RESID && t + RD - 1 < NT) load_r((t + RD - 1) % RD, t + RD - 1);
+                    if (EPI == GS_EPI_RESID) load_r(t);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const f32x4_t b4 = *(const f32x4_t *)&bs[32 * t + 8 * q + 4 * g];
@@ -665,7 +653,7 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                             *(uint4 *)(Cp + m * 2 * N + (int64_t)((n0 >> 5) + wc * NT + t) * 64 + 8 * seg) = make_uint4(lo.x, lo.y, hi.x, hi.y);
                         } else {
                             f32x4_t o = {__uint_as_float(lo.x), __uint_as_float(lo.y), __uint_as_float(hi.x), __uint_as_float(hi.y)};
-                            if (EPI == GS_EPI_RESID) o += rq[t % RD][k];
+                            if (EPI == GS_EPI_RESID) o += rq[k];
                             *(f32x4_t *)(C + m * N + n0 + (wc * NT + t) * 32 + 4 * seg) = o;
                             if constexpr (STATS) {
                                 const float d0 = o[0] - st_s[k], d1 = o[1] - st_s[k], d2 = o[2] - st_s[k], d3 = o[3] - st_s[k];
@@ -741,29 +729,20 @@ __global__ __launch_bounds__(64 * WR * WC) void k_gemm_split(const void *__restr
         Wp += k0;
         Cv = (void *)((float *)Cv + (int64_t)blockIdx.y * c_slice);
     }
-    constexpr bool HALF_OK = NT % 2 == 0 && (WC * (NT / 2) * 32) % (16 * WR * WC) == 0;       // the half tile's weight staging plan exists
-    constexpr int NH = HALF_OK ? NT / 2 : NT;
+    constexpr int COLS = WC * NT * 32, HALF_COLS = gs_half_cols(NT, WR, WC);
+    constexpr int NH = HALF_COLS ? NT / 2 : NT;
     const int xcd = (int)(blockIdx.x & 7);
     typename gs_xf<MR>::type xf, xg;
     int par = 0;
     bool primed = false;
-    struct Tile { int64_t tm; int n0; bool half, valid; };
-    auto decode = [&](int64_t qv) {
-        Tile t;
-        t.half = HALF_OK && qv >= q_full;
-        const int64_t qt = t.half ? q_full + ((qv - q_full) >> 1) : qv;
-        t.tm = (qt / n_tiles_n) * 8 + xcd;
-        t.n0 = (int)(qt % n_tiles_n) * (WC * NT * 32) + (t.half ? (int)((qv - q_full) & 1) * (WC * NH * 32) : 0);
-        t.valid = qv < q_virtual && t.tm < n_tiles_m;
-        return t;
-    };
+    auto decode = [&](int64_t qv) { return gs_tile_of(n_tiles_n, n_tiles_m, q_full, q_virtual, COLS, HALF_COLS, xcd, qv); };
     // the whole (padded) bias row, once per workgroup, behind the epilogue's tile blocks
     char *epi_lds = (char *)Ws + epi_off;
     float *bias_lds = (float *)(epi_lds + (WR * WC) * (32 * 136));
     for (int e = threadIdx.x; e < n_tiles_n * (WC * NT * 32); e += 64 * WR * WC) bias_lds[e] = (bias && e < N) ? bias[e] : 0.f;
     __syncthreads();
     for (int64_t qv = blockIdx.x >> 3; qv < q_virtual; qv += per_round) {
-        const Tile cur = decode(qv), nxt = decode(qv + per_round);
+        const GsTile cur = decode(qv), nxt = decode(qv + per_round);
         if (!cur.valid) { primed = false; continue; }
         const bool has_next = nxt.valid && nxt.half == cur.half && !(MR == 1 && NT == 1 && WR == 1);      // (the few-rows tile does not chain)
         const int prof_idx = (int)(qv * 8 + xcd);
@@ -809,9 +788,9 @@ __device__ __forceinline__ void atts_issue_loads(typename gs_u32vec<4 * NLD>::ty
     }
 }
 
-// PF: the next item's K / V pieces are loaded into registers before the strips of the current one (needs the register budget of
-// one wavefront per SIMD); otherwise an item's loads are waited for on the spot
-template <int NT, int NW, bool PF>
+// An item's K / V loads are waited for on the spot.  (Holding the next item's pieces in registers during the strips of the current one
+// needs the register budget of one wavefront per SIMD — 4 wavefronts, 454 / 472 registers — and was slower.)
+template <int NT, int NW>
 __global__ __launch_bounds__(64 * NW) void k_attention_split(const uint16_t *__restrict__ qkv, int T, int H, int items,
                                                              uint16_t *__restrict__ out, float out_scale, int *work)
 {
@@ -832,18 +811,12 @@ __global__ __launch_bounds__(64 * NW) void k_attention_split(const uint16_t *__r
     const int nstrip = (T + 15) >> 4;
     typename gs_u32vec<4 * NLD>::type k8, v8;
 
-    int item = blockIdx.x;
-    if (work) {
-        if (tid == 0) s_ticket = atomicAdd(&work[0], 1);
-        __syncthreads();
-        item = s_ticket;
-    }
-    if (PF) atts_issue_loads<NLD, NTHR>(k8, v8, qkv, item < items ? item : items - 1, T, H, tid);
+    int item = att_first_item(work, s_ticket, tid);
     int nxt = item;
     for (; item < items; item = nxt) {
         const int b = item / H, h = item % H;
         const uint16_t *Qp = qkv + (int64_t)b * T * tok_stride + (int64_t)2 * h * 64;
-        if (!PF) atts_issue_loads<NLD, NTHR>(k8, v8, qkv, item, T, H, tid);
+        atts_issue_loads<NLD, NTHR>(k8, v8, qkv, item, T, H, tid);
         __syncthreads();                                            // the previous item's strips are done with LDS
 #pragma unroll
         for (int r = 0; r < NLD; ++r) {
@@ -866,7 +839,7 @@ __global__ __launch_bounds__(64 * NW) void k_attention_split(const uint16_t *__r
                 }
             }
         }
-        if (work && tid == 0) s_ticket = atomicAdd(&work[0], 1);    // everyone has read the previous ticket (barrier above)
+        att_take_ticket(work, s_ticket, tid);
         // query fragments of the wavefront's first strip: lane (n, g) = query q0 + n, dims [32 kk + 8 g, + 8) of either piece
         u32x4_t qh[2], ql[2];
         {
@@ -876,8 +849,7 @@ __global__ __launch_bounds__(64 * NW) void k_attention_split(const uint16_t *__r
             for (int kk = 0; kk < 2; ++kk) { qh[kk] = *(const u32x4_t *)(qr + kk * 64); ql[kk] = *(const u32x4_t *)(qr + kk * 64 + 32); }
         }
         __syncthreads();
-        nxt = work ? s_ticket : item + (int)gridDim.x;
-        if (PF) atts_issue_loads<NLD, NTHR>(k8, v8, qkv, nxt < items ? nxt : items - 1, T, H, tid);      // in flight during the strips below
+        nxt = att_next_item(work, s_ticket, item);
 #pragma unroll 1
         for (int si = 0; si < NSTRIP; ++si) {
             const int strip = wave + NW * si;
@@ -993,15 +965,7 @@ __global__ __launch_bounds__(64 * NW) void k_attention_split(const uint16_t *__r
             }
         }
     }
-    // the last workgroup to leave re-arms the counters for the next launch on this stream
-    if (work && tid == 0) {
-        __threadfence();
-        if (atomicAdd(&work[1], 1) == (int)gridDim.x - 1) {
-            work[0] = 0;
-            work[1] = 0;
-            __threadfence();
-        }
-    }
+    att_rearm(work, tid);
 }
 
 // The epilogue of a split-K GEMM (few rows): out = epilogue(sum over the S partial results, in slice order, + bias) — the same
@@ -1031,17 +995,6 @@ __global__ __launch_bounds__(GS_TPB) void k_splitk_finish(const float *__restric
     }
 }
 
-// current device ordinal and its CU count (cached per ordinal; kernel attributes and the persistent grids are per device)
-static bsc_status gs_device(int *dev, int *n_cu)
-{
-    static int cus[64] = {0};
-    BSC_HIP(hipGetDevice(dev));
-    int &c = cus[*dev & 63];
-    if (!c) BSC_HIP(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, *dev));
-    *n_cu = c;
-    return BSC_OK;
-}
-
 extern "C" bsc_status bsc_enc_attention_split(const void *qkv_pieces_dev, int32_t B, int32_t T, int32_t heads, int32_t head_dim,
                                               void *out_pieces_dev, float out_scale, int32_t *work2_dev, void *hip_stream)
 {
@@ -1055,22 +1008,20 @@ extern "C" bsc_status bsc_enc_attention_split(const void *qkv_pieces_dev, int32_
     BSC_TRY(gs_device(&dev, &n_cu));
     const int64_t items = (int64_t)B * heads;
     const dim3 grid((unsigned)(items < n_cu ? items : n_cu));
-#define BSC_ATT_LAUNCH(NTV, NWV, PFV)                                                                                                   \
+#define BSC_ATT_LAUNCH(NTV, NWV)                                                                                                        \
     do {                                                                                                                             \
         constexpr int TPv = NTV * 16, VPv = 4 * (((TPv / 4 - 1) | 7) + 1) + 8;                                                       \
         const size_t lds = (size_t)2 * (TPv * 72 + 64 * VPv) * sizeof(uint16_t);                                                     \
         static uint64_t attr_set = 0;       /* bit per device ordinal */                                                              \
         if (!(attr_set >> (dev & 63) & 1)) {                                                                                         \
-            BSC_HIP(hipFuncSetAttribute((const void *)k_attention_split<NTV, NWV, PFV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            BSC_HIP(hipFuncSetAttribute((const void *)k_attention_split<NTV, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             attr_set |= 1ull << (dev & 63);                                                                                          \
         }                                                                                                                            \
-        hipLaunchKernelGGL((k_attention_split<NTV, NWV, PFV>), grid, dim3(64 * NWV), lds, s, (const uint16_t *)qkv_pieces_dev, T, heads,  \
+        hipLaunchKernelGGL((k_attention_split<NTV, NWV>), grid, dim3(64 * NWV), lds, s, (const uint16_t *)qkv_pieces_dev, T, heads, \
                            (int)items, (uint16_t *)out_pieces_dev, out_scale, (int *)work2_dev);                                     \
     } while (0)
-    // 4 wavefronts, one per SIMD, with the 512-register budget: the next item's K / V pieces wait in registers during the strips
-    static const int att_mode = getenv("BSC_ATT_SPLIT_MODE") ? atoi(getenv("BSC_ATT_SPLIT_MODE")) : 0;
-    if (T <= 224) { if (att_mode == 1) BSC_ATT_LAUNCH(14, 4, true); else BSC_ATT_LAUNCH(14, 7, false); }
-    else { if (att_mode == 1) BSC_ATT_LAUNCH(18, 4, true); else BSC_ATT_LAUNCH(18, 8, false); }
+    if (T <= 224) BSC_ATT_LAUNCH(14, 7);
+    else BSC_ATT_LAUNCH(18, 8);
 #undef BSC_ATT_LAUNCH
     BSC_HIP(hipGetLastError());
     return BSC_OK;
@@ -1092,81 +1043,24 @@ extern "C" bsc_status bsc_enc_gemm_split_ws(const void *a_dev, int64_t M, int32_
                                             int32_t epilogue, int32_t a_mode, float c_pieces_scale, float *ln_stats_dev,
                                             float *ln_mu_dev, float ln_eps, void *ws_dev, int64_t ws_bytes, void *hip_stream)
 {
-    if (!a_dev || !pieces_dev || !c_dev || M <= 0 || N <= 0 || K <= 0 || (K % GS_KC) || epilogue < 0 || epilogue > 3 ||
-        a_mode < 0 || a_mode > 2 || (epilogue == GS_EPI_RESID && !resid_dev) || (c_pieces_scale != 0.f && (N % 32))) {
-        bsc_set_error("bsc_enc_gemm_split: invalid argument (K must be a multiple of 32; piece output needs N %% 32 == 0)");
+    if (!a_dev || !pieces_dev || !c_dev || (epilogue == GS_EPI_RESID && !resid_dev)) {
+        bsc_set_error("bsc_enc_gemm_split: invalid argument (null operand, or the residual epilogue without residual rows)");
         return BSC_E_INVALID;
     }
-    if (epilogue == GS_EPI_RESID && c_pieces_scale != 0.f) { bsc_set_error("bsc_enc_gemm_split: the residual epilogue writes f32"); return BSC_E_INVALID; }
-    const bool ln = a_mode == GS_A_LN, stats = epilogue == GS_EPI_RESID && ln_stats_dev != nullptr;
-    if ((ln || stats) && (!ln_stats_dev || !ln_mu_dev)) {
-        bsc_set_error("bsc_enc_gemm_split_ln: the LayerNorm modes need both ln_stats_dev and ln_mu_dev");
-        return BSC_E_INVALID;
-    }
-    if (ln && (K % 128 || K > 1024 || epilogue == GS_EPI_RESID || c_pieces_scale == 0.f)) {
-        // (an f32-output form was measured and dropped: fc1 2 497 -> 2 687 us, its epilogue holds the tile twice)
-        bsc_set_error("bsc_enc_gemm_split_ln: a_mode 2 reads rows of width K = 128 .. 1024 (multiple of 128) and writes pieces (epilogue 0 / 1)");
-        return BSC_E_INVALID;
-    }
-    if (stats && (N % 128 || N > 1024 || a_mode == GS_A_LN)) {
-        bsc_set_error("bsc_enc_gemm_split_ln: row statistics ride on the residual epilogue of a GEMM with N = 128 .. 1024 (multiple of 128)");
-        return BSC_E_INVALID;
-    }
-    // tile shape: 256 x 256 (8 wavefronts x 32 rows x 256 columns), or — for the narrow outputs (N <= 1024: 888 tiles of 256 x 256 on
-    // 256 CUs is 3.47 rounds, 13 % of the last one idle) — a smaller tile that balances better; BSC_GEMM_TILE = 1 / 3 / 4 forces one
-    static const int tile_env = getenv("BSC_GEMM_TILE") ? atoi(getenv("BSC_GEMM_TILE")) : 0;
-    // Few rows (a frame or a handful per call: M = 197 .. ~3 500): 256-row tiles leave N / 256 = 3 .. 12 workgroups on 256 CUs and a
-    // forward of ONE frame took 6 ms (3x PyTorch's f32 GEMMs).  Tile 6 = 32 rows x 128 columns, four wavefronts side by side on the
-    // columns (each 32 x 32): 60 KB of LDS, two or three workgroups per CU cover each other's chunk latency (a 32-row tile has 6
-    // MFMAs per chunk to hide a weight chunk's round trip behind).  While even those tiles do not fill the chip, K is split over
-    // grid.y: every slice writes an f32 partial result, k_splitk_finish adds them in slice order (deterministic) and applies the
-    // epilogue.  Per flop the small tile moves 8x the weight bytes through LDS, so it is taken only while the big tiles would not fill
-    // the chip once.  (LayerNorm-in-the-load and the statistics epilogue exist for the big tile only: callers with few rows use the
-    // LayerNorm pass.)
     int dev = 0, n_cu = 0;
     BSC_TRY(gs_device(&dev, &n_cu));
-    const int64_t big_tiles = ((M + 255) / 256) * ((N + 255) / 256);
-    const bool few_rows = !(ln || stats) && !tile_env && big_tiles <= n_cu && M <= 8192;
-    // (32-row tiles re-read the weights once per 32 rows: from ~500 rows on the launch is bound by that L2 traffic — 4.6 TB/s at
-    //  1 576 rows — and 128 x 128 tiles, 4 wavefronts x 32 rows x 128 columns, take over, with the same split-K)
-    const int tile = (ln || stats) ? 1 : few_rows ? (M <= 512 ? 6 : 3) : tile_env ? tile_env : (N <= 1024 ? BSC_GEMM_NARROW_TILE : 1);
-    const int TROWS = tile == 6 ? 32 : tile == 3 ? 128 : 256, TCOLS = tile == 1 ? 256 : 128, NTHR = (tile == 3 || tile == 6) ? 256 : 512;
-    const int64_t n_pad = ((int64_t)N + 255) / 256 * 256;
-    const int n_tiles_n = (int)(n_pad / TCOLS);
-    const int64_t n_tiles_m = (M + TROWS - 1) / TROWS;
-    const int64_t groups = (n_tiles_m + 7) / 8;                    // row tiles per XCD
-    // a last round that fills at most half of the CUs runs as half-width tiles (tile 1 only; BSC_GEMM_TAIL=0: whole tiles)
-    static const int tail_env = getenv("BSC_GEMM_TAIL") ? atoi(getenv("BSC_GEMM_TAIL")) : 1;
-    // persistent workgroups: one per CU; the 60 KB few-rows tile two per CU
-    const int64_t q_all = groups * n_tiles_n, per_round = ((tile == 6 || tile == 3) ? 2 : 1) * (n_cu / 8 > 0 ? n_cu / 8 : 1);
-    const int64_t q_rem = q_all % per_round;
-    const int64_t q_full = (tile == 1 && tail_env && q_rem > 0 && 2 * q_rem <= per_round && q_all > per_round) ? q_all - q_rem : q_all;
-    const int64_t q_virtual = q_full + 2 * (q_all - q_full);
-    const int64_t n_wg = (q_virtual < per_round ? q_virtual : per_round) * 8;     // persistent: one workgroup per CU
-    const size_t lds_loop = (size_t)2 * 2 * TCOLS * ((BSC_GEMM_W_DMA && tile != 6) ? GS_KC : GS_PITCH) * sizeof(uint16_t);
-    const size_t lds_epi = (size_t)(NTHR / 64) * (32 * 136);                      // the epilogue's per-wavefront tile blocks
-    const size_t lds = lds_loop + lds_epi + (size_t)n_pad * sizeof(float);        // + the bias row
-    if (lds > 160 * 1024) { bsc_set_error("bsc_enc_gemm_split: N = %d does not fit the kernel's LDS plan (bias row)", N); return BSC_E_INVALID; }
+    const bool ln = a_mode == GS_A_LN, stats = epilogue == GS_EPI_RESID && ln_stats_dev != nullptr;
+    GsPlan p;
+    const char *why = nullptr;
+    if (!gs_plan(M, K, N, epilogue, a_mode, c_pieces_scale != 0.f, ln_stats_dev && ln_mu_dev, stats, ws_dev ? ws_bytes : 0, n_cu, &p, &why)) {
+        bsc_set_error("%s (M %lld, K %d, N %d)", why, (long long)M, K, N);
+        return BSC_E_INVALID;
+    }
     hipStream_t s = (hipStream_t)hip_stream;
     const bool ap = a_mode == GS_A_PIECES;
-    // split-K of the few-rows tile: the largest slice count that keeps the launch within two workgroups per CU, slices of whole
-    // chunks, at least two chunks each
-    int S = 1;
-    if (few_rows && (N % 4) == 0 && !getenv("BSC_GEMM_NO_SPLITK")) {
-        static const int cand[] = {24, 16, 12, 8, 6, 4, 3, 2};
-        for (int c : cand)
-            if (K % (GS_KC * c) == 0 && K / c >= 2 * GS_KC && n_tiles_m * n_tiles_n * c <= 2 * (int64_t)n_cu) { S = c; break; }
-    }
-    // f32 partial results live in the caller's workspace (stream-ordered, capture-safe: the library allocates nothing here); a
-    // workspace that is absent or too small means fewer slices
-    while (S > 1 && (!ws_dev || (int64_t)S * M * N * (int64_t)sizeof(float) > ws_bytes)) {
-        int nxt_s = 1;
-        static const int cand2[] = {16, 12, 8, 6, 4, 3, 2};
-        for (int c : cand2) if (c < S && K % (GS_KC * c) == 0 && K / c >= 2 * GS_KC) { nxt_s = c; break; }
-        S = nxt_s;
-    }
+    const int tile = p.tile, S = p.S;
+    // split-K: the slices leave f32 partial results in the workspace (plain epilogue, no bias); k_splitk_finish applies the caller's
     float *part = S > 1 ? (float *)ws_dev : nullptr;
-    const int k_len = K / S;
     const float *bias_l = S > 1 ? nullptr : bias_dev, *resid_l = S > 1 ? nullptr : resid_dev;
     void *c_l = S > 1 ? (void *)part : c_dev;
     const float cps_l = S > 1 ? 0.f : c_pieces_scale;
@@ -1177,19 +1071,18 @@ extern "C" bsc_status bsc_enc_gemm_split_ws(const void *a_dev, int64_t M, int32_
         static uint64_t attr_set = 0;       /* bit per device ordinal */                                                              \
         if (!(attr_set >> (dev & 63) & 1)) {                                                                                         \
             BSC_HIP(hipFuncSetAttribute((const void *)k_gemm_split<MRV, NTV, WRV, WCV, EPIV, AMV, CPV, STV>,                         \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                      \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_MAX));                                      \
             attr_set |= 1ull << (dev & 63);                                                                                          \
         }                                                                                                                            \
-        hipLaunchKernelGGL((k_gemm_split<MRV, NTV, WRV, WCV, EPIV, AMV, CPV, STV>), dim3((unsigned)n_wg, (unsigned)S), dim3(NTHR),   \
-                           lds, s, a_dev, M, k_len, (const uint16_t *)pieces_dev, n_pad * K, N, bias_l, resid_l, c_l, a_scale,       \
-                           out_scale, cps_l, n_tiles_n, (int)n_tiles_m, q_full, q_virtual, (int)per_round, (int)lds_loop,             \
-                           ln_stats_dev, ln_mu_dev, ln_eps, K, (int64_t)M * N);                                                       \
+        hipLaunchKernelGGL((k_gemm_split<MRV, NTV, WRV, WCV, EPIV, AMV, CPV, STV>), dim3((unsigned)p.n_wg, (unsigned)S),             \
+                           dim3(p.threads), (size_t)p.lds, s, a_dev, M, p.k_len, (const uint16_t *)pieces_dev, p.n_pad * K, N,       \
+                           bias_l, resid_l, c_l, a_scale, out_scale, cps_l, p.n_tiles_n, (int)p.n_tiles_m, p.q_full, p.q_virtual,    \
+                           (int)p.per_round, (int)p.lds_loop, ln_stats_dev, ln_mu_dev, ln_eps, K, (int64_t)M * N);                   \
     } while (0)
 #define BSC_GEMM_LAUNCH(EPIV, AMV, CPV)                                                                                              \
     do {                                                                                                                             \
         if (tile == 6) BSC_GEMM_LAUNCH2(1, 1, 1, 4, EPIV, AMV, CPV, false);                                                          \
         else if (tile == 3) BSC_GEMM_LAUNCH2(1, 4, 4, 1, EPIV, AMV, CPV, false);                                                     \
-        else if (tile == 4) BSC_GEMM_LAUNCH2(1, 4, 8, 1, EPIV, AMV, CPV, false);                                                     \
         else BSC_GEMM_LAUNCH2(1, 8, 8, 1, EPIV, AMV, CPV, false);                                                                    \
     } while (0)
     if (ln) {                           // LayerNorm folded into the operand load: qkv (bias) and fc1 (bias + GELU), piece output
@@ -1239,7 +1132,7 @@ extern "C" bsc_status bsc_enc_gemm_split_ws(const void *a_dev, int64_t M, int32_
         static uint64_t host[GS_PROF_MAX][6];
         BSC_HIP(hipStreamSynchronize(s));
         BSC_HIP(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_prof), sizeof(host)));
-        const int64_t n = q_virtual * 8 < GS_PROF_MAX ? q_virtual * 8 : GS_PROF_MAX;
+        const int64_t n = p.q_virtual * 8 < GS_PROF_MAX ? p.q_virtual * 8 : GS_PROF_MAX;
         for (int64_t w = 0; w < n; ++w)
             fprintf(stderr, "GP %lld %llx %llu %llu %llu %llu %llu\n", (long long)w, (unsigned long long)host[w][0], (unsigned long long)host[w][1],
                     (unsigned long long)host[w][2], (unsigned long long)host[w][3], (unsigned long long)host[w][4], (unsigned long long)host[w][5]);

@@ -4,6 +4,7 @@
 //     s = x + delta (bf16) ; y = LayerNorm(s) * gamma + beta            one wavefront per token row
 // Stateless entry point, launched on the caller's stream (captured into the encoder's HIP graph).
 #include "bsc_internal.h"
+#include "att_ticket.h"
 
 #define TPB 256
 
@@ -710,12 +711,8 @@ __device__ __forceinline__ void att_issue_loads(typename u32vec<4 * NLD>::type &
 // NT key tiles of 16 (even): sequence length <= 16 * NT.  NW wavefronts, each takes the query strips w, w + NW, ...
 // Persistent workgroups: a workgroup walks (image, head) items and issues the global loads of its NEXT item (K, V and
 // its wavefronts' query strips, into registers) before it computes the current one out of LDS, so the HBM-bound load
-// phase and the issue-bound compute phase overlap instead of alternating chip-wide.  Items are handed out by a ticket
-// counter (work[0]; work[1] counts finished workgroups, the last one re-arms both), not by a static stride: a workgroup
-// whose CU is shared with another stream's kernel simply takes fewer items.  With the static stride one slow or late
-// workgroup stretched the whole launch — the rgb chain of libbscnav's own side stream, resident on one or two CUs for
-// milliseconds, cost the 12 attention launches of a ViT-B forward 2.4 ms (bench pipeline 24.7 -> 22.x ms per step).
-// work == nullptr keeps the static stride.
+// phase and the issue-bound compute phase overlap instead of alternating chip-wide.  Items are handed out by tickets
+// (att_ticket.h); work == nullptr keeps a static stride.
 template <int NT, int NW>
 __global__ __launch_bounds__(64 * NW) void k_attention(const uint16_t *__restrict__ qkv, int T, int H, int items,
                                                        uint16_t *__restrict__ out, int *work)
@@ -738,12 +735,7 @@ __global__ __launch_bounds__(64 * NW) void k_attention(const uint16_t *__restric
     typename u32vec<4 * NLD>::type k8, v8, q8;
 
     // software pipeline over the workgroup's items; the prefetch past the last item re-reads the last one (harmless)
-    int item = blockIdx.x;
-    if (work) {
-        if (tid == 0) s_ticket = atomicAdd(&work[0], 1);
-        __syncthreads();
-        item = s_ticket;
-    }
+    int item = att_first_item(work, s_ticket, tid);
     att_issue_loads<NLD, NTHR>(k8, v8, q8, qkv, item < items ? item : items - 1, T, H, tid);
     int nxt = item;
     for (; item < items; item = nxt) {
@@ -770,9 +762,9 @@ __global__ __launch_bounds__(64 * NW) void k_attention(const uint16_t *__restric
                 }
             }
         }
-        if (work && tid == 0) s_ticket = atomicAdd(&work[0], 1);    // everyone has read the previous ticket (barrier above)
+        att_take_ticket(work, s_ticket, tid);
         __syncthreads();
-        nxt = work ? s_ticket : item + (int)gridDim.x;
+        nxt = att_next_item(work, s_ticket, item);
         att_issue_loads<NLD, NTHR>(k8, v8, q8, qkv, nxt < items ? nxt : items - 1, T, H, tid);      // in flight during the strips below
 #pragma unroll
         for (int si = 0; si < NSTRIP; ++si) {
@@ -872,15 +864,7 @@ __global__ __launch_bounds__(64 * NW) void k_attention(const uint16_t *__restric
             }
         }
     }
-    // the last workgroup to leave re-arms the counters for the next launch on this stream
-    if (work && tid == 0) {
-        __threadfence();
-        if (atomicAdd(&work[1], 1) == (int)gridDim.x - 1) {
-            work[0] = 0;
-            work[1] = 0;
-            __threadfence();
-        }
-    }
+    att_rearm(work, tid);
 }
 
 // ---- the same attention on 32 x 32 x 16 MFMA tiles (sequences up to 224 tokens) ----------------------------------------------
@@ -950,12 +934,7 @@ __global__ __launch_bounds__(64 * NW) void k_attention32(const uint16_t *__restr
     const float c = 0.125f * 1.44269504088896340736f;               // 1/sqrt(64) * log2(e)
     u32vec<16>::type k8, v8, bqn;
 
-    int item = blockIdx.x;
-    if (work) {
-        if (tid == 0) s_ticket = atomicAdd(&work[0], 1);
-        __syncthreads();
-        item = s_ticket;
-    }
+    int item = att_first_item(work, s_ticket, tid);
     att32_load_range<0, 12>(k8, v8, bqn, qkv, item < items ? item : items - 1, T, H, tid);
     int nxt = item;
 #ifdef BSC_ATT_PROFILE
@@ -985,9 +964,9 @@ __global__ __launch_bounds__(64 * NW) void k_attention32(const uint16_t *__restr
                 *(uint2 *)&sVt[(ch * 8 + 2 * e + 1) * VP + t0] = make_uint2((w0 >> 16) | (w1 & 0xffff0000u), (w2 >> 16) | (w3 & 0xffff0000u));
             }
         }
-        if (work && tid == 0) s_ticket = atomicAdd(&work[0], 1);    // everyone has read the previous ticket (barrier above)
+        att_take_ticket(work, s_ticket, tid);
         __syncthreads();
-        nxt = work ? s_ticket : item + (int)gridDim.x;
+        nxt = att_next_item(work, s_ticket, item);
         const int nxc = nxt < items ? nxt : items - 1;
         ATT_T(1)
         const int q0 = wave * 32;
@@ -1120,15 +1099,7 @@ __global__ __launch_bounds__(64 * NW) void k_attention32(const uint16_t *__restr
                tph[0], tph[1], tph[2], tph[3], tph[4], tph[5], tph[6]);
 #endif
 #undef ATT_T
-    // the last workgroup to leave re-arms the counters for the next launch on this stream
-    if (work && tid == 0) {
-        __threadfence();
-        if (atomicAdd(&work[1], 1) == (int)gridDim.x - 1) {
-            work[0] = 0;
-            work[1] = 0;
-            __threadfence();
-        }
-    }
+    att_rearm(work, tid);
 }
 
 extern "C" bsc_status bsc_enc_attention_dyn(const void *qkv_dev, int32_t B, int32_t T, int32_t heads, int32_t head_dim,
@@ -1140,20 +1111,12 @@ extern "C" bsc_status bsc_enc_attention_dyn(const void *qkv_dev, int32_t B, int3
         return BSC_E_INVALID;
     }
     hipStream_t s = (hipStream_t)hip_stream;
-    static int n_cu = 0;                // one workgroup per CU (its LDS footprint allows no second one)
-    if (!n_cu) {
-        int dev = 0;
-        BSC_HIP(hipGetDevice(&dev));
-        BSC_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    int dev = 0, n_cu = 0;              // one workgroup per CU of the CURRENT device (its LDS footprint allows no second one)
+    BSC_TRY(gs_device(&dev, &n_cu));
     const int64_t items = (int64_t)B * heads;
     const dim3 grid((unsigned)(items < n_cu ? items : n_cu));
-    static const bool tiles32 = !(getenv("BSC_ATT_TILE") && atoi(getenv("BSC_ATT_TILE")) == 16);
-    if (T <= 224 && tiles32)
+    if (T <= 224)
         hipLaunchKernelGGL((k_attention32<7, 7>), grid, dim3(64 * 7), 0, s, (const uint16_t *)qkv_dev, T, heads, (int)items,
-                           (uint16_t *)out_dev, (int *)work2_dev);
-    else if (T <= 224)
-        hipLaunchKernelGGL((k_attention<14, 7>), grid, dim3(64 * 7), 0, s, (const uint16_t *)qkv_dev, T, heads, (int)items,
                            (uint16_t *)out_dev, (int *)work2_dev);
     else
         hipLaunchKernelGGL((k_attention<18, 8>), grid, dim3(64 * 8), 0, s, (const uint16_t *)qkv_dev, T, heads, (int)items,

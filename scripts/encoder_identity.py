@@ -1,7 +1,9 @@
-"""Two builds of libbscnav.so in ONE process: the split GEMM's outputs must be bit-identical (torch.equal) on the forward's four
-GEMM calls (qkv, fc1 with the LayerNorm in the load; proj, fc2 with the residual epilogue + row statistics) and on the edge shapes
-of tests/test_gpu_gemm_split_dma.py; then the four calls are timed, the two builds alternating.
-usage: gemm_dma_identity.py OTHER_LIB.so [frames]      (the build under test is the one _lib loads: BSC_LIB_PATH or the product)"""
+"""Two builds of libbscnav.so in ONE process: the encoder kernels' outputs must be bit-identical (torch.equal) — the split GEMM on
+the forward's four GEMM calls (qkv, fc1 with the LayerNorm in the load; proj, fc2 with the residual epilogue + row statistics) and
+on the edge shapes of tests/test_gpu_gemm_split_dma.py, the attention launches (bsc_enc_attention_dyn, bsc_enc_attention_split) at
+T = 197 and 261 with a few more items than CUs, with the ticket pair and without.  Then the four calls, and the f32 forward at
+`frames` frames, are timed with the two builds alternating.
+usage: encoder_identity.py OTHER_LIB.so [frames] [turns]   (the build under test is the one _lib loads: BSC_LIB_PATH or the product)"""
 import ctypes as C
 import os
 import sys
@@ -92,6 +94,33 @@ for M, N in ((8200, 256), (8449, 2304), (8200, 2336)):
                  *both(lambda: (sl(x, epi), sl(x, epi, c_pieces_scale=2.0), sl(xp, epi, a_scale=4.0, a_pieces=True, c_pieces_scale=2.0))))
             same(f"M={M} N={N} K={K} epilogue={epi} LayerNorm in the load", *both(lambda: (sll(x, epi, a_ln=True, ln_stats=st, ln_mu=mu, c_pieces_scale=2.0),)))
 
+# ---- attention ---------------------------------------------------------------------------------------------------------------------
+def attention(kind, x, B, T, H, ticket):
+    lib = _lib.load()
+    work = torch.zeros(2, dtype=torch.int32, device="cuda") if ticket else None
+    wp = C.c_void_p(work.data_ptr()) if ticket else None
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    out = torch.zeros(B * T, (1 if kind == "dyn" else 2) * H * 64, dtype=torch.int16, device="cuda")
+    if kind == "dyn":
+        _lib.check(lib.bsc_enc_attention_dyn(C.c_void_p(x.data_ptr()), B, T, H, 64, C.c_void_p(out.data_ptr()), wp, stream))
+    else:
+        _lib.check(lib.bsc_enc_attention_split(C.c_void_p(x.data_ptr()), B, T, H, 64, C.c_void_p(out.data_ptr()), 16.0, wp, stream))
+    torch.cuda.synchronize()
+    return (out.view(torch.float16),) + ((work.to(torch.float32),) if ticket else ())
+
+
+n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+for T in (197, 261):
+    H = 3
+    B = (n_cu + 5 + H - 1) // H
+    torch.manual_seed(T)
+    qkv = torch.randn(B, T, 3, H, 64, device="cuda") * 1.5
+    xb = qkv.bfloat16().contiguous()
+    xs = encoder.split_rows(qkv.view(B * T, 3 * H * 64), 1.0)
+    for ticket in (True, False):
+        same(f"bsc_enc_attention_dyn T={T} items={B * H} ticket={ticket}", *both(lambda: attention("dyn", xb, B, T, H, ticket)))
+        same(f"bsc_enc_attention_split T={T} items={B * H} ticket={ticket}", *both(lambda: attention("split", xs, B, T, H, ticket)))
+
 # ---- the forward's four calls ------------------------------------------------------------------------------------------------------
 M, Wd = frames * 197, 768
 u0 = torch.randn(M, Wd, device="cuda")
@@ -134,4 +163,28 @@ for name, fn in calls:
             t[key].append(timeit(fn))
     use(new)
     print(f"{name}: other build {' '.join(f'{v:7.1f}' for v in t['old'])} us | this build {' '.join(f'{v:7.1f}' for v in t['new'])} us", flush=True)
-sys.exit(1 if bad else 0)
+
+# ---- the f32 forward, the two builds alternating: turns of about a second; the other build's own spread is the noise of this run --------
+turns = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+vit = encoder.RandomViT("vit_b16", image_size=224, seed=0, dtype=torch.float32).cuda()
+rgb = torch.randint(0, 255, (frames, 480, 640, 4), dtype=torch.uint8, device="cuda")
+outs = both(lambda: (vit.patch_tokens(rgb).clone(),))
+same(f"f32 forward, {frames} frames", *outs)
+del outs
+use(new)
+per = timeit(lambda: vit.patch_tokens(rgb), 2)
+reps = max(2, int(round(1e6 / per)))
+t = {"new": [], "old": []}
+for _ in range(turns):
+    for key, lib in (("old", old), ("new", new)):
+        use(lib)
+        t[key].append(timeit(lambda: vit.patch_tokens(rgb), reps) / 1e3)
+use(new)
+med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+spread = max(t["old"]) - min(t["old"])
+print(f"forward {frames} frames, {turns} turns of {reps} forwards, ms: other build {' '.join(f'{v:.3f}' for v in t['old'])} | this build "
+      f"{' '.join(f'{v:.3f}' for v in t['new'])}", flush=True)
+print(f"forward medians: other build {med['old']:.3f} ms, this build {med['new']:.3f} ms; spread of the other build's turns {spread:.3f} ms -> "
+      f"{'within the spread' if med['new'] - med['old'] <= spread else 'SLOWER by more than the spread'}", flush=True)
+slow = med["new"] - med["old"] > spread
+sys.exit(1 if bad or slow else 0)

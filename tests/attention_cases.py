@@ -85,17 +85,14 @@ def reference(q, k, v, want_p=True):
 # (2^-24 each) — stays below 2^-16 A.
 #
 # Measured on an MI355X (256 CUs) against the fp64 reference — never against another run of a kernel —, the worst over every
-# launch of tests/test_gpu_attention.py (tile edges, up to 1281 items of 288 tokens, ticket and stride, the A/B children).
+# launch of tests/test_gpu_attention.py (tile edges, up to 1281 items of 288 tokens, ticket and stride).
 # Worst |out - ref| / bf16_bound:          random  uniform  negative  match
 #   k_attention32<7, 7>   (T <= 224)        0.857    0.437     0.694      0
-#   k_attention<14, 7>    (BSC_ATT_TILE=16) 0.857    0.349     0.663      0
 #   k_attention<18, 8>    (T > 224)         0.717    0.437     0.555      0
 # k_attention_split, worst max|out - ref| / its limit max(2 e32, 2^-20 max(1, max|ref|)) (e32: torch's f32 op against fp64):
 #                            random            random_f32        uniform           negative          match
-#   <14, 7, false>           2.5e-6 / 4.4e-6   4.3e-6 / 6.1e-6   4.2e-8 / 9.5e-7   1.5e-6 / 4.0e-6   9.5e-7 / 7.8e-6
-#   <18, 8, false>           2.2e-6 / 4.2e-6   3.5e-6 / 6.1e-6   5.3e-9 / 9.5e-7   1.5e-6 / 4.1e-6   9.5e-7 / 8.0e-6
-#   <14, 4, true>  (MODE=1)  3.4e-6 / 9.7e-6   1.8e-6 / 6.0e-6   4.2e-8 / 9.5e-7   1.5e-6 / 4.0e-6   9.5e-7 / 9.6e-6
-#   <18, 4, true>  (MODE=1)  2.1e-6 / 5.9e-6   2.0e-6 / 4.9e-6   5.0e-9 / 9.5e-7   1.4e-6 / 4.3e-6   9.5e-7 / 8.6e-6
+#   <14, 7>                  2.5e-6 / 4.4e-6   4.3e-6 / 6.1e-6   4.2e-8 / 9.5e-7   1.5e-6 / 4.0e-6   9.5e-7 / 7.8e-6
+#   <18, 8>                  2.2e-6 / 4.2e-6   3.5e-6 / 6.1e-6   5.3e-9 / 9.5e-7   1.5e-6 / 4.1e-6   9.5e-7 / 8.0e-6
 #   e32 of those launches: 2.1e-6 .. 4.9e-6 (random, random_f32, negative), 1.2e-8 (uniform), below 1e-13 (match).
 def bf16_bound(ref, A):
     return 2.0 ** -8 * (A + ref.abs()) + 2.0 ** -16 * A

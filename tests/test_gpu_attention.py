@@ -1,8 +1,7 @@
 """The in-tree attention kernels (csrc/encoder_ops.hip: k_attention32, k_attention; csrc/encoder_gemm.hip: k_attention_split)
 against an fp64 reference on the generated cases of tests/attention_cases.py: every key-tile and mask edge, launches that
 give a workgroup a second and later (image, head) item — with the ticket pair and with the static stride —, the ticket
-pair's re-arming, guard rows around the output, rejected arguments, and the A/B variants (BSC_ATT_TILE=16,
-BSC_ATT_SPLIT_MODE=1), each in an interpreter of its own.
+pair's re-arming, guard rows around the output and rejected arguments.
 
 bf16 kernels: |out - ref| <= bf16_bound elementwise (attention_cases.bf16_bound, derived from the kernels' arithmetic).
 split kernel: max|out - ref| <= max(2 e32, 2^-20 max(1, max|ref|)), e32 the error of PyTorch's own f32
@@ -10,10 +9,8 @@ scaled_dot_product_attention against fp64 (the yardstick of tests/test_gpu_encod
 pieces hold (22 bits) with a factor of two."""
 import ctypes as C
 import functools
-import os
 import zlib
 
-import numpy as np
 import pytest
 
 import attention_cases as AC
@@ -211,61 +208,3 @@ def test_rejected_arguments_launch_nothing(T, head_dim):
         st, buf = launch(kernel, qkv, 1, T, 2, work, head_dim=head_dim, entry=entry)
         assert st == -1, (kernel, entry, st)                        # BSC_E_INVALID
         assert bool((buf == SENTINEL).all()) and work.tolist() == [0, 0]
-
-
-# ---- A/B variants ---------------------------------------------------------------------------------------------------------------------
-def _variant_cases(kernel):
-    n = n_cu()
-    edges = [1, 17, 192, 193, 224] + ([225, 256, 257, 288] if kernel == "split" else [])
-    cases = [(1, T, 2, fam, True, "edge") for T in edges for fam in families_of(kernel)]
-    for count in ("n_cu+1", "2n_cu+3"):
-        B, H = items_of(count)
-        for T in (17, 193):
-            for fam in ("random", "negative"):
-                cases += [(B, T, H, fam, True, count), (B, T, H, fam, False, count)]
-    return n, cases
-
-
-def _npy(tmp, kernel, B, T, H):
-    return os.path.join(tmp, f"{kernel}_{B}_{T}_{H}.npy")
-
-
-def _variant_child(kernel, tmp):
-    """Runs in the child interpreter, under the variant's switch: the reduced list through check(), and every `random` output
-    against the default variant's (the parent's .npy): both are within one bound of one reference."""
-    import torch
-    n, cases = _variant_cases(kernel)
-    differing = 0
-    for B, T, H, fam, ticket, label in cases:
-        work = torch.zeros(2, dtype=torch.int32, device="cuda") if ticket else None
-        items = B * H
-        samples = sorted({0, n - 1, n, items - 1}) if items > n else ()
-        body = check(kernel, B, T, H, fam, work, samples, label="variant " + label)
-        if fam == "random":
-            z = case(fam, B, T, H)
-            base = torch.from_numpy(np.load(_npy(tmp, kernel, B, T, H))).cuda()
-            d = (decode(kernel, body, B, T, H).double() - decode(kernel, base, B, T, H).double()).abs()
-            if kernel == "bf16":
-                assert bool((d <= 2.0 * z["bound"]).all()), (B, T, H)
-            else:
-                assert d.max().item() <= z["limit"], (B, T, H, d.max().item())
-            differing += int((body != base).sum().item())
-    print("differing elements against the default variant:", differing)
-
-
-@pytest.mark.parametrize("kernel,knob", [("bf16", "BSC_ATT_TILE=16"), ("split", "BSC_ATT_SPLIT_MODE=1")])
-def test_ab_variants_keep_the_result(kernel, knob, tmp_path):
-    """k_attention<14, 7> (BSC_ATT_TILE=16) and k_attention_split<14 | 18, 4, true> (BSC_ATT_SPLIT_MODE=1: the next item's K / V
-    wait in registers) are shipped and otherwise never launched.  The switches are read once per process: an interpreter each."""
-    import subprocess
-    import sys
-    for B, T, H, fam, ticket, label in _variant_cases(kernel)[1]:
-        if fam == "random" and not os.path.exists(_npy(str(tmp_path), kernel, B, T, H)):
-            np.save(_npy(str(tmp_path), kernel, B, T, H), check(kernel, B, T, H, fam, None, label="default " + label).cpu().numpy())
-    name, val = knob.split("=")
-    code = ("import sys; sys.path[:0] = ['.', 'tests', 'tests/golden']; import test_gpu_attention as t; "
-            f"t._variant_child({kernel!r}, {str(tmp_path)!r}); print('ok')")
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **{name: val}),
-                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True, timeout=300)
-    print(r.stdout[-6000:])
-    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]

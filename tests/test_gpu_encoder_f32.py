@@ -278,10 +278,12 @@ def test_patch_matrix_as_padded_pieces(arch):
 
 
 @pytest.mark.parametrize("M,K,N,epilogue", [(197, 768, 2304, 0), (261, 4096, 1024, 2), (1576, 768, 3072, 1)])
-def test_few_rows_gemm_without_split_k(M, K, N, epilogue, monkeypatch):
-    """the few-rows tiles on their own (BSC_GEMM_NO_SPLITK: what a caller without a workspace gets) against the split-K route"""
+def test_few_rows_gemm_without_split_k(M, K, N, epilogue):
+    """the few-rows tiles on their own — what a caller without a workspace gets (bsc_enc_gemm_split, the entry point that takes
+    none) — against the split-K route"""
+    import ctypes as C
     import torch
-    from bsc_nav_amd import encoder
+    from bsc_nav_amd import _lib, encoder
     torch.manual_seed(M + K)
     lin = torch.nn.Linear(K, N).cuda().float()
     torch.nn.init.trunc_normal_(lin.weight, std=0.02)
@@ -289,8 +291,12 @@ def test_few_rows_gemm_without_split_k(M, K, N, epilogue, monkeypatch):
     R = torch.randn(M, N, device="cuda")
     sl = encoder.SplitLinear(lin)
     a = sl(A, epilogue, resid=R.clone() if epilogue == 2 else None)
-    monkeypatch.setenv("BSC_GEMM_NO_SPLITK", "1")
-    b = sl(A, epilogue, resid=R.clone() if epilogue == 2 else None)
+    b = torch.empty((M, N), dtype=torch.float32, device="cuda")
+    Rb = R.clone()
+    _lib.check(_lib.load().bsc_enc_gemm_split(
+        C.c_void_p(A.data_ptr()), M, K, C.c_void_p(sl.pieces.data_ptr()), N, C.c_void_p(sl.bias.data_ptr()),
+        C.c_void_p(Rb.data_ptr()) if epilogue == 2 else None, C.c_void_p(b.data_ptr()), 1.0, 1.0 / sl.scale, epilogue, 0, 0.0,
+        C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     ref = A.double() @ lin.weight.double().t() + lin.bias.double()
     if epilogue == 1:
         ref = torch.nn.functional.gelu(ref, approximate="tanh")

@@ -33,7 +33,7 @@ def _check_stats(stats, mu, u, Wd):
 
 
 # Which tile a call takes (bsc_enc_gemm_split_ws): with ln_stats always the 256 x 256 one; without, the few-rows tiles need
-# M <= 8192, so M >= 8193 takes the 256 x 256 tile too (BSC_GEMM_NARROW_TILE = 1).
+# M <= 8192, so M >= 8193 takes the 256 x 256 tile too (gs_plan, csrc/gemm_split_plan.h).
 #   (8200, 128, 128)  n_pad = 256 > N: the wavefront's column tiles 4 .. 7 lie beyond N
 #   (8200, 768, 64)   two chunks: the shortest loop whose tiles chain (the next tile's chunk 0 lands under the second, last chunk)
 #   (999, 768, 768)   statistics only (999 rows without them are a few-rows call); last row tile partly filled
