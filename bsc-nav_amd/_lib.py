@@ -33,6 +33,11 @@ class BscRegion(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class BscBand(C.Structure):
+    """struct bsc_band: the stored heights lo <= h <= hi of one slice of bsc_topdown_slices (8 bytes; lo > hi: every height)."""
+    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32)]
+
+
 DRAW_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32))
 
 # every symbol include/bscnav.h declares: name -> (restype, argtypes)
@@ -68,6 +73,8 @@ SIGNATURES = {
     "bsc_localize": (_I32, [_VP, _VP, _I32, _I32, _F64, _VP, _I32, _I32, _VP, _VP, _VP]),
     "bsc_localize_regions": (_I32, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "bsc_score_map": (_I32, [_VP, _VP, _I32, _VP, _VP, _VP]),
+    "bsc_topdown_slices": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP]),
+    "bsc_topdown_rebuild": (_I32, [_VP, _I32, _I32]),
     "bsc_cluster_centers": (_I32, [_VP, _I32, _I32, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
     "bsc_cluster_centers_batch": (_I32, [_VP, _I32, _I32, _VP, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
     "bsc_frontier_mask": (_I32, [_VP, _VP, _VP]),

@@ -223,6 +223,8 @@ struct bsc_ctx {
     int32_t last_counts[1024];
     u64 *sm_map;                    // bsc_score_map scratch: packed (score, height) keys of one chunk of queries (score_map.hip)
     int64_t sm_cap;                 // bytes
+    u64 *td_mask;                   // bsc_topdown_* scratch: column occupancy bits, (gs, gs, ceil(nh / 64)), then the call's bands (topdown.hip)
+    int64_t td_cap;                 // bytes
     ClusterWs *clus;                // bsc_cluster_centers / bsc_cluster_centers_batch workspace (nullptr until the first call)
     // frontier helpers (allocated on first use, gs*gs each)
     bool fr_ready;             // all of them exist (frontier.hip fr_alloc)
@@ -412,6 +414,10 @@ struct RegionScan;
 BSC_LOCAL bsc_status region_scan(bsc_ctx *x, const float *q_dev, int32_t nq, const bsc_region *regions, RegionScan *out);
 // bsc_score_map behind its argument checks (score_map.hip)
 bsc_status score_map_impl(bsc_ctx *x, const float *q_dev, int32_t nq, const bsc_region *regions, float *score_dev, int32_t *height_dev);
+// bsc_topdown_slices / bsc_topdown_rebuild behind their argument checks (topdown.hip): n_bands slices of the stored voxels into the
+// outputs given (device pointers, any may be null; hmap_out: the packed word of x->hmap).  bands_host == nullptr: one open band.
+bsc_status topdown_impl(bsc_ctx *x, int32_t n_bands, const bsc_band *bands_host, uint8_t *rgb_out, int32_t *height_out,
+                        int32_t *count_out, u64 *hmap_out);
 // ---- the cosine scan (cosine_scan.hip), as localize.hip calls it ----
 int64_t sims_row_stride(int64_t n_rows);   // floats between the similarity rows of consecutive queries
 // q_dev (nq, D) -> x->l_q: normalised, zero-padded to the whole query tiles the matrix-core kernels read

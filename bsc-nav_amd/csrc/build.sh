@@ -11,7 +11,7 @@ FLAGS="${BSC_EXTRA_FLAGS} --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contra
 ROCM="${ROCM_PATH:-$(dirname "$(dirname "$(readlink -f "$(command -v hipcc)")")")}"
 # *.cpp: host-only C++ for plain g++ — host_rng (NumPy's MT19937 shuffle restated, AVX2 paths behind a runtime check), ctx_mem
 # (the ledger of a context's device / pinned-host memory: the declarations of the HIP runtime API, no device code)
-SOURCES="host_rng.cpp ctx_mem.cpp prims.hip radix.hip ingest.hip dense.hip flush.hip store_compact.hip surprise.hip cosine_scan.hip localize.hip score_map.hip cluster.hip frontier.hip encoder_ops.hip encoder_gemm.hip capi.hip"
+SOURCES="host_rng.cpp ctx_mem.cpp prims.hip radix.hip ingest.hip dense.hip flush.hip store_compact.hip surprise.hip cosine_scan.hip localize.hip score_map.hip topdown.hip cluster.hip frontier.hip encoder_ops.hip encoder_gemm.hip capi.hip"
 pids=()
 objs=()
 for f in $SOURCES; do

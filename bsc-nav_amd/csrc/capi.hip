@@ -1134,6 +1134,24 @@ extern "C" bsc_status bsc_score_map(bsc_ctx *x, const float *q_dev, int32_t nq, 
     return score_map_impl(x, q_dev, nq, regions_host, score_dev, height_dev);
 }
 
+extern "C" bsc_status bsc_topdown_slices(bsc_ctx *x, int32_t n_bands, const bsc_band *bands_host, uint8_t *rgb_dev, int32_t *height_dev,
+                                         int32_t *count_dev)
+{
+    if (!x) { bsc_set_error("bsc_topdown_slices: NULL context"); return BSC_E_INVALID; }
+    if (n_bands < 1 || n_bands > 256) { bsc_set_error("bsc_topdown_slices: n_bands=%d (1..256)", n_bands); return BSC_E_INVALID; }
+    if (!rgb_dev && !height_dev && !count_dev) { bsc_set_error("bsc_topdown_slices: every output is NULL"); return BSC_E_INVALID; }
+    BSC_HIP(hipSetDevice(x->device));
+    return topdown_impl(x, n_bands, bands_host, rgb_dev, height_dev, count_dev, nullptr);
+}
+
+extern "C" bsc_status bsc_topdown_rebuild(bsc_ctx *x, int32_t lo, int32_t hi)
+{
+    if (!x) { bsc_set_error("bsc_topdown_rebuild: NULL context"); return BSC_E_INVALID; }
+    BSC_HIP(hipSetDevice(x->device));
+    const bsc_band b = {lo, hi};
+    return topdown_impl(x, 1, &b, x->cv_map, nullptr, nullptr, x->hmap);
+}
+
 // ---- multi-GPU merge helpers (dense modes) ---------------------------------------------------------------
 __global__ __launch_bounds__(TPB) void k_dense_gather(int64_t n, const int32_t *__restrict__ keys, int gs, int nh,
                                                       const int32_t *__restrict__ occ, const float *__restrict__ acc,

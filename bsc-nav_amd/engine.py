@@ -72,6 +72,30 @@ def score_map_regions(Q, radius=None, curr=None, floor=None):
     return region_array(Q, radius, curr, floor)
 
 
+BAND_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32)])          # struct bsc_band
+assert BAND_DTYPE.itemsize == C.sizeof(_lib.BscBand) == 8
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def band_array(bands=None):
+    """The (S,) bsc_band array of VoxelEngine.topdown_slices from its argument (needs no context): None — a NULL pointer, one
+    open band — or a sequence of (lo, hi) pairs / Nones, None being an open band (lo > hi: every height).  One (lo, hi) pair of
+    numbers is one band.  Bounds beyond int32 are clamped to it; an entry that is no pair raises ValueError (an empty sequence gives
+    an empty array, which the library refuses like more than 256 bands)."""
+    if bands is None:
+        return None
+    bands = list(bands)
+    if len(bands) == 2 and all(np.isscalar(v) for v in bands):
+        bands = [tuple(bands)]
+    out = np.zeros(len(bands), BAND_DTYPE)
+    for i, b in enumerate(bands):
+        if b is not None and len(b) != 2:
+            raise ValueError(f"bands[{i}]: expected (lo, hi) or None")
+        lo, hi = (0, -1) if b is None else (int(b[0]), int(b[1]))
+        out["lo"][i], out["hi"][i] = min(max(lo, INT32_MIN), INT32_MAX), min(max(hi, INT32_MIN), INT32_MAX)
+    return out
+
+
 def pad_cluster_batch(pos, sim, counts=None):
     """The (pos (Q,K,3) int32, sim (Q,K) float32, counts (Q,) int32) arrays of VoxelEngine.cluster_centers_batch from its
     arguments (needs no context).  pos / sim are either arrays of those shapes, with counts (None: K points each, otherwise
@@ -404,6 +428,30 @@ class VoxelEngine:
         _lib.check(self.lib.bsc_score_map(self.h, _dp(q), Q, _hp(regions), _dp(score), _dp(height)))
         self._leave()
         return score, height
+
+    def topdown_slices(self, bands=None, heights=True, counts=True):
+        """Top-down maps of height bands from the stored voxels (bsc_topdown_slices): bands a list of (lo, hi) — stored heights
+        lo <= h <= hi, None or lo > hi: every height — or None for one open band
+        -> dict(rgb (S,gs,gs,3) u8, height (S,gs,gs) i32, count (S,gs,gs) i32) of CUDA tensors; height / count are None when
+        heights / counts is False.  rgb[s,r,c] is grid_rgb of the highest stored voxel of column (r,c) inside band s (zeros: none),
+        height its h (-1: none), count the stored voxels of the column inside the band.  The resident cv_map / max_height and the
+        results of the last localize call are untouched."""
+        arr = band_array(bands)
+        S, gs = 1 if arr is None else len(arr), self.cfg.grid_size
+        rgb = torch.empty((S, gs, gs, 3), dtype=torch.uint8, device=self.device)
+        height = torch.empty((S, gs, gs), dtype=torch.int32, device=self.device) if heights else None
+        count = torch.empty((S, gs, gs), dtype=torch.int32, device=self.device) if counts else None
+        self._enter(rgb, height, count)
+        _lib.check(self.lib.bsc_topdown_slices(self.h, S, _hp(arr), _dp(rgb), _dp(height), _dp(count)))
+        self._leave()
+        return dict(rgb=rgb, height=height, count=count)
+
+    def rebuild_topdown(self, band=None):
+        """The slice of `band` ((lo, hi); None: every height) becomes the resident top-down state (bsc_topdown_rebuild): cv_map
+        the slice colours, max_height the slice heights (-inf: none) with tie order 0 as after import_heightmap — what
+        export_heightmap, frontier_mask and frontier_clusters read, and what a later ingest continues from."""
+        b = band_array([band])[0]
+        _lib.check(self.lib.bsc_topdown_rebuild(self.h, int(b["lo"]), int(b["hi"])))
 
     def cluster_centers(self, pos=None, sim=None, K=None, query_index=0, eps=10.0, min_samples=5):
         """BSCAgent.weighted_cluster_centers on the GPU -> (centers (n,3) f64, labels (K,) int, sizes list).

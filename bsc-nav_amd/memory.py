@@ -16,7 +16,7 @@ import torch
 
 from . import floors, store
 from .config import from_namespace
-from .engine import VoxelEngine
+from .engine import INT32_MIN, VoxelEngine
 from .geometry import PoseChain, cam_mat_fov, sample_indices_fast as sample_indices
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -423,6 +423,35 @@ class VoxelTokenMemory:
         if floors is None and getattr(self.args, "load_single_floor", False) and hasattr(self, "floor_min_height"):
             floors = [(self.floor_min_height, self.floor_max_height)] * Q
         return self.engine.score_map(q, radius=region_radius, curr=curr_grid, floor=floors)
+
+    def _default_band(self):
+        """The loaded single floor's z-band exactly when voxel_localized applies it (args.load_single_floor), otherwise None."""
+        if getattr(self.args, "load_single_floor", False) and hasattr(self, "floor_min_height"):
+            return (self.floor_min_height, self.floor_max_height)
+        return None
+
+    def topdown_maps(self, bands=None):
+        """Top-down maps of the stored voxels per height band (VoxelEngine.topdown_slices) — the floor plan voxel_score_map's
+        field is laid over.  bands: a list of (lo, hi) stored heights / None (every height); None: the loaded single floor
+        (args.load_single_floor) when one was selected, otherwise one open band
+        -> dict(rgb (S,gs,gs,3) u8 in RGB order, height (S,gs,gs) i32, count (S,gs,gs) i32) torch tensors on the device."""
+        if bands is None:
+            bands = [self._default_band()]
+        return self.engine.topdown_slices(bands)
+
+    def rgb_2d_map(self, height):
+        """TrajectoryDrawer._get_rgb_2d_map (BSCAgent.py:203-234): per column the colour of the highest stored voxel at or below
+        the cut floor(height / cs - minh) -> (gs,gs,3) uint8 NumPy array in BGR order, zeros where the column holds none."""
+        cut = int(np.floor((height / self.cs) - self.minh))
+        rgb = self.engine.topdown_slices([(INT32_MIN, cut)], heights=False, counts=False)["rgb"][0]
+        return np.ascontiguousarray(rgb.cpu().numpy()[..., ::-1])
+
+    def rebuild_topdown_map(self, band=None):
+        """cv_map / max_height become the top-down map of the stored voxels inside `band` ((lo, hi); None: the default of
+        topdown_maps) — what a memory from load_memory or merge_shards, whose map is empty, needs before the frontier calls
+        (VoxelEngine.rebuild_topdown).  Nothing calls this on its own."""
+        self.engine.rebuild_topdown(self._default_band() if band is None else band)
+        self._touch()
 
     def weighted_cluster_centers(self, top_k_positions, top_k_similarity, eps=10, min_samples=5):
         """GESObjectNavRobot.weighted_cluster_centers (BSCAgent.py:479-497) on the GPU: DBSCAN over the top-K voxel

@@ -233,6 +233,36 @@ bsc_status bsc_score_map(bsc_ctx *ctx, const float *q_dev, int32_t n_queries,
                          const bsc_region *regions_host /* (Q) or NULL: no region for any query */,
                          float *score_dev /* (Q, gs, gs) f32 */, int32_t *height_dev /* (Q, gs, gs) i32, may be NULL */);
 
+/* Top-down maps of a height band from the STORED voxels: TrajectoryDrawer._get_rgb_2d_map (BSCAgent.py:203-234: per column the
+ * colour of the highest stored voxel at or below a cut, there a Python loop over all max_id voxels) for any number of bands in
+ * one call — what bsc_score_map's field is laid over, the floor plan of one floor (the z-band of memory_2.py:202-252).  The
+ * resident cv_map / max_height (memory_2.py:98-100,901-903) is the map of the POINTS as they arrived: it exists only while frames
+ * are ingested, is reset by the imports, and knows no ceiling.
+ * For band s and cell (r, c) let B be the stored voxels (id < max_id) at row r, column c with lo_s <= h <= hi_s, h being the third
+ * coordinate of grid_rgb_pos (after the -min_h shift).
+ *   rgb_dev[s, r, c, :]   grid_rgb of the voxel of B with the largest h, in RGB order; 0, 0, 0 when B is empty
+ *   height_dev[s, r, c]   that h; -1 when B is empty
+ *   count_dev[s, r, c]    |B|
+ * A cell's voxel is the one occupied_ids names (positions are distinct in every state the library builds).  A band with lo > hi
+ * means every height; bands may reach outside [0, max_h - min_h): they are clipped, and one entirely outside is empty.
+ * bands_host NULL: every band is open (one open band with n_bands 1).  The outputs are caller-owned device buffers indexed in 64 bits; any may
+ * be NULL but not all three.  All three modes; an empty memory gives BSC_OK and zeros / -1 / 0.  The call first completes both
+ * library streams (the rgb chain writes colours on the side stream) and returns after its own work has completed; the result is
+ * bit-reproducible.  The resident cv_map / max_height and the resident results of the last localize call are untouched.  The
+ * occupancy bits the kernels work from (grid_size^2 * ceil((max_h - min_h) / 64) * 8 bytes, whatever n_bands) are scratch of the
+ * context.  BSC_E_INVALID, nothing written: a NULL context, n_bands outside 1..256, all outputs NULL.
+ *
+ * bsc_topdown_rebuild makes the slice of the band lo <= h <= hi (lo > hi: every height) the context's top-down state, on the
+ * device: max_height[r, c] = that h with tie order 0, exactly what bsc_import_heightmap leaves for it, -inf where the band holds
+ * nothing; cv_map = the slice colours.  bsc_export_heightmap, bsc_frontier_mask and bsc_frontier_clusters then work on the slice
+ * — after load_memory, bsc_dense_replace_full or a merge, which leave the map empty — and a later bsc_ingest continues with the
+ * reference's height >= max_height rule (memory_2.py:901-903). */
+typedef struct bsc_band { int32_t lo, hi; } bsc_band;     /* 8 bytes; stored heights lo <= h <= hi; lo > hi: every height */
+bsc_status bsc_topdown_slices(bsc_ctx *ctx, int32_t n_bands, const bsc_band *bands_host /* (S) or NULL: one open band */,
+                              uint8_t *rgb_dev /* (S,gs,gs,3) u8 */, int32_t *height_dev /* (S,gs,gs) or NULL */,
+                              int32_t *count_dev /* (S,gs,gs) or NULL */);
+bsc_status bsc_topdown_rebuild(bsc_ctx *ctx, int32_t lo, int32_t hi);
+
 /* GESObjectNavRobot.weighted_cluster_centers (BSCAgent.py:479-497), the consumer of voxel_localized's output:
  * DBSCAN(eps, min_samples) over K top-ranked positions (scikit-learn semantics), similarity-weighted centres,
  * clusters ordered by mean similarity (stable, descending).  pos_host (K,3) / sim_host (K) NULL = cluster the first K
