@@ -75,6 +75,7 @@ SIGNATURES = {
     "bsc_score_map": (_I32, [_VP, _VP, _I32, _VP, _VP, _VP]),
     "bsc_topdown_slices": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP]),
     "bsc_topdown_rebuild": (_I32, [_VP, _I32, _I32]),
+    "bsc_render_views": (_I32, [_VP, _I32, _VP, _VP, _I32, _I32, _F64, _F64, _VP, _VP, _VP, _VP]),
     "bsc_cluster_centers": (_I32, [_VP, _I32, _I32, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
     "bsc_cluster_centers_batch": (_I32, [_VP, _I32, _I32, _VP, _VP, _VP, _F64, _I32, _VP, _VP, _VP, _VP]),
     "bsc_frontier_mask": (_I32, [_VP, _VP, _VP]),

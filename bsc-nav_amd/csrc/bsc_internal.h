@@ -225,6 +225,8 @@ struct bsc_ctx {
     int64_t sm_cap;                 // bytes
     u64 *td_mask;                   // bsc_topdown_* scratch: column occupancy bits, (gs, gs, ceil(nh / 64)), then the call's bands (topdown.hip)
     int64_t td_cap;                 // bytes
+    u64 *rv_words;                  // bsc_render_views scratch: occupancy bits per 4 x 4 x 4 brick, then the call's transforms (render.hip)
+    int64_t rv_cap;                 // bytes
     ClusterWs *clus;                // bsc_cluster_centers / bsc_cluster_centers_batch workspace (nullptr until the first call)
     // frontier helpers (allocated on first use, gs*gs each)
     bool fr_ready;             // all of them exist (frontier.hip fr_alloc)
@@ -418,6 +420,10 @@ bsc_status score_map_impl(bsc_ctx *x, const float *q_dev, int32_t nq, const bsc_
 // outputs given (device pointers, any may be null; hmap_out: the packed word of x->hmap).  bands_host == nullptr: one open band.
 bsc_status topdown_impl(bsc_ctx *x, int32_t n_bands, const bsc_band *bands_host, uint8_t *rgb_out, int32_t *height_out,
                         int32_t *count_out, u64 *hmap_out);
+// bsc_render_views behind its argument checks (render.hip): kinv is the matrix to use, band_host may be null (every height), the
+// outputs are device pointers (any may be null)
+bsc_status render_impl(bsc_ctx *x, int32_t n_views, const double *transforms_host, const double *kinv, int32_t height, int32_t width,
+                       double t_min, double t_max, const bsc_band *band_host, int32_t *voxel_out, float *depth_out, uint8_t *rgb_out);
 // ---- the cosine scan (cosine_scan.hip), as localize.hip calls it ----
 int64_t sims_row_stride(int64_t n_rows);   // floats between the similarity rows of consecutive queries
 // q_dev (nq, D) -> x->l_q: normalised, zero-padded to the whole query tiles the matrix-core kernels read

@@ -1152,6 +1152,44 @@ extern "C" bsc_status bsc_topdown_rebuild(bsc_ctx *x, int32_t lo, int32_t hi)
     return topdown_impl(x, 1, &b, x->cv_map, nullptr, nullptr, x->hmap);
 }
 
+extern "C" bsc_status bsc_render_views(bsc_ctx *x, int32_t n_views, const double *transforms_host, const double *kinv_host, int32_t height,
+                                       int32_t width, double t_min, double t_max, const bsc_band *band_host, int32_t *voxel_dev,
+                                       float *depth_dev, uint8_t *rgb_dev)
+{
+    if (!x || !transforms_host) { bsc_set_error("bsc_render_views: NULL context or transforms"); return BSC_E_INVALID; }
+    if (n_views < 1 || n_views > 1024) { bsc_set_error("bsc_render_views: n_views=%d (1..1024)", n_views); return BSC_E_INVALID; }
+    if (height < 1 || height > 4096 || width < 1 || width > 4096) {
+        bsc_set_error("bsc_render_views: height=%d, width=%d (1..4096 each)", height, width);
+        return BSC_E_INVALID;
+    }
+    if (!voxel_dev && !depth_dev && !rgb_dev) { bsc_set_error("bsc_render_views: every output is NULL"); return BSC_E_INVALID; }
+    if (!(t_min >= 0.0 && t_min < t_max && isfinite(t_max))) {
+        bsc_set_error("bsc_render_views: t_min=%g, t_max=%g (0 <= t_min < t_max, both finite)", t_min, t_max);
+        return BSC_E_INVALID;
+    }
+    for (int64_t i = 0; i < (int64_t)n_views * 16; ++i)
+        if (!isfinite(transforms_host[i])) {
+            bsc_set_error("bsc_render_views: transform %d holds a non-finite entry", (int)(i / 16));
+            return BSC_E_INVALID;
+        }
+    if (kinv_host) {
+        for (int i = 0; i < 9; ++i)
+            if (!isfinite(kinv_host[i])) { bsc_set_error("bsc_render_views: kinv holds a non-finite entry"); return BSC_E_INVALID; }
+        if (kinv_host[6] != 0.0 || kinv_host[7] != 0.0 || kinv_host[8] != 1.0) {
+            bsc_set_error("bsc_render_views: the last row of kinv is not [0, 0, 1] (the ray parameter would not be the depth)");
+            return BSC_E_INVALID;
+        }
+    }
+    if (x->c.grid_size & 1) {
+        // row = int(gs/2 - trunc(x/cs)) truncates a second time at row 0 when gs/2 is no integer: a second irregular cell
+        bsc_set_error("bsc_render_views: grid_size=%d is odd (the truncation cells of an odd grid are not supported)", x->c.grid_size);
+        return BSC_E_INVALID;
+    }
+    BSC_HIP(hipSetDevice(x->device));
+    return render_impl(x, n_views, transforms_host, kinv_host ? kinv_host : x->c.Kinv, height, width, t_min, t_max, band_host, voxel_dev,
+                       depth_dev, rgb_dev);
+}
+
 // ---- multi-GPU merge helpers (dense modes) ---------------------------------------------------------------
 __global__ __launch_bounds__(TPB) void k_dense_gather(int64_t n, const int32_t *__restrict__ keys, int gs, int nh,
                                                       const int32_t *__restrict__ occ, const float *__restrict__ acc,

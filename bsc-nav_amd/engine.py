@@ -453,6 +453,33 @@ class VoxelEngine:
         b = band_array([band])[0]
         _lib.check(self.lib.bsc_topdown_rebuild(self.h, int(b["lo"]), int(b["hi"])))
 
+    def render_views(self, transforms, size=None, kinv=None, band=None, t_range=None, want=("voxel", "depth", "rgb")):
+        """The stored voxels seen from camera poses (bsc_render_views): transforms (V,4,4) or (4,4) f64, camera to map, as ingest
+        takes them; size (H, W), None: the context's frame size; kinv the (3,3) inverse intrinsics with last row [0,0,1], None: the
+        context's own; band (lo, hi) stored heights, None: every height; t_range (t_min, t_max) along the ray, in depth units,
+        None: the configuration's (min_depth, max_depth)
+        -> dict(voxel (V,H,W) i32, depth (V,H,W) f32, rgb (V,H,W,3) u8) of CUDA tensors, None for what `want` does not name.
+        Per pixel the first stored voxel the ray meets: its id (-1: none), the depth where the ray enters its cell (0: none) and
+        grid_rgb of it (zeros: none)."""
+        T = np.ascontiguousarray(np.asarray(transforms, np.float64).reshape(-1, 16))
+        V = len(T)
+        H, W = (self.cfg.height, self.cfg.width) if size is None else (int(size[0]), int(size[1]))
+        kinv = None if kinv is None else np.ascontiguousarray(np.asarray(kinv, np.float64).reshape(9))
+        arr = band_array(None if band is None else [band])
+        t_min, t_max = (self.cfg.min_depth, self.cfg.max_depth) if t_range is None else (float(t_range[0]), float(t_range[1]))
+        unknown = set(want) - {"voxel", "depth", "rgb"}
+        if unknown:
+            raise ValueError(f"want: {sorted(unknown)} (voxel, depth, rgb)")
+        shape = (V, max(H, 0), max(W, 0))                         # (a size the library refuses still reaches it)
+        voxel = torch.empty(shape, dtype=torch.int32, device=self.device) if "voxel" in want else None
+        depth = torch.empty(shape, dtype=torch.float32, device=self.device) if "depth" in want else None
+        rgb = torch.empty(shape + (3,), dtype=torch.uint8, device=self.device) if "rgb" in want else None
+        self._enter(voxel, depth, rgb)
+        _lib.check(self.lib.bsc_render_views(self.h, V, _hp(T), _hp(kinv), H, W, t_min, t_max, _hp(arr), _dp(voxel), _dp(depth),
+                                             _dp(rgb)))
+        self._leave()
+        return dict(voxel=voxel, depth=depth, rgb=rgb)
+
     def cluster_centers(self, pos=None, sim=None, K=None, query_index=0, eps=10.0, min_samples=5):
         """BSCAgent.weighted_cluster_centers on the GPU -> (centers (n,3) f64, labels (K,) int, sizes list).
         pos/sim None: cluster the first K results of query `query_index` of the last localize call (no host copy)."""

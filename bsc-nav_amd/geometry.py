@@ -71,6 +71,15 @@ class PoseChain:
         self.tf = self.inv_init_base_tf @ base_pose
         return np.ascontiguousarray(self.tf @ B @ self.base2cam_tf)
 
+    def transform_of(self, pose):
+        """The matrix pc_transform would return for `pose`, without moving the map: self.tf stays as the last ingested frame left
+        it and an unanchored chain is not anchored (RuntimeError: there is no map frame yet)."""
+        if self.inv_init_base_tf is None:
+            raise RuntimeError("PoseChain.transform_of: no map frame yet (nothing ingested and no anchor set)")
+        B = self.base_transform
+        base_pose = B @ pose_vec2tf(pose) @ np.linalg.inv(B)
+        return np.ascontiguousarray((self.inv_init_base_tf @ base_pose) @ B @ self.base2cam_tf)
+
 
 def sample_indices(n_pixels, rate):
     """The reference's shuffled sub-sampling (memory_2.py:747-749); consumes np.random's global stream identically."""

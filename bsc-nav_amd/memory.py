@@ -439,6 +439,35 @@ class VoxelTokenMemory:
             bands = [self._default_band()]
         return self.engine.topdown_slices(bands)
 
+    def _render(self, pose, size, fov, band, max_range, want):
+        """render_view / visible_voxels: the engine call for one pose -> dict of CUDA tensors with the view axis dropped"""
+        T = self.chain.transform_of(np.asarray(pose, dtype=np.float64))         # (the map does not move: chain.tf and the anchor stay)
+        kinv = None
+        if size is not None or fov is not None:
+            h, w = (self.cfg.height, self.cfg.width) if size is None else (int(size[0]), int(size[1]))
+            kinv = np.linalg.inv(cam_mat_fov(h, w, fov=90 if fov is None else fov))
+        out = self.engine.render_views(T[None], size=size, kinv=kinv, band=self._default_band() if band is None else band,
+                                       t_range=None if max_range is None else (self.min_depth, float(max_range)), want=want)
+        return {k: (None if v is None else v[0]) for k, v in out.items()}
+
+    def render_view(self, pose, size=None, fov=None, band=None, max_range=None):
+        """The memory seen from `pose` (given as obs2voxeltoken takes it; VoxelEngine.render_views): per pixel the first stored
+        voxel the ray meets -> dict(voxel (H,W) i32 ids, -1: none; depth (H,W) f32 in the parametrisation of a depth image, 0: none;
+        rgb (H,W,3) u8 in RGB order) of NumPy arrays.  size (H, W) and fov build the intrinsics with cam_mat_fov (None, None: the
+        frames' own; a quarter-size preview is size=(120, 160)); band (lo, hi) stored heights, None: the loaded single floor
+        (args.load_single_floor) when one was selected, otherwise every height; max_range replaces max_depth.  The map does not
+        move; RuntimeError before the first frame (there is no map frame to place the pose in)."""
+        out = self._render(pose, size, fov, band, max_range, ("voxel", "depth", "rgb"))
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def visible_voxels(self, pose, size=None, fov=None, band=None, max_range=None):
+        """The stored voxels in view at `pose` (arguments as render_view) -> (positions (n,3) int64 rows of grid_rgb_pos,
+        pixel_counts (n,) int64: how many pixels show each), in ascending voxel id order."""
+        ids = self._render(pose, size, fov, band, max_range, ("voxel",))["voxel"]
+        ids, counts = torch.unique(ids[ids >= 0], return_counts=True)
+        ids = ids.cpu().numpy().astype(np.int64)
+        return np.asarray(self.grid_rgb_pos, np.int64)[ids].reshape(-1, 3), counts.cpu().numpy().astype(np.int64)
+
     def rgb_2d_map(self, height):
         """TrajectoryDrawer._get_rgb_2d_map (BSCAgent.py:203-234): per column the colour of the highest stored voxel at or below
         the cut floor(height / cs - minh) -> (gs,gs,3) uint8 NumPy array in BGR order, zeros where the column holds none."""

@@ -263,6 +263,36 @@ bsc_status bsc_topdown_slices(bsc_ctx *ctx, int32_t n_bands, const bsc_band *ban
                               int32_t *count_dev /* (S,gs,gs) or NULL */);
 bsc_status bsc_topdown_rebuild(bsc_ctx *ctx, int32_t lo, int32_t hi);
 
+/* The stored voxels seen from a camera pose: per pixel the first stored voxel its ray meets — the inverse of bsc_ingest's geometry
+ * (utils.py:153-214 depth2pc, transform_pc, base_pos2grid_id_3d; memory_2.py:859-875,755-756), for a viewer's first-person image of
+ * the memory, the set of voxels in view at a pose, and a range image to hold against an observed depth image pixel by pixel.
+ * Ray.  Pixel (x, y) of view v has the ray p(t) = o + t d with o = T[:3,3] and d = T[:3,:3] (K^-1 (x + 0.5, y + 0.5, 1)); T is
+ *   transforms_host[v], the row-major 4x4 camera-to-map transform bsc_ingest takes (pc_transform, memory_2.py:860).  K^-1 has the
+ *   last row [0, 0, 1], so t is the depth z of depth2pc.  kinv_host NULL: the context's own K^-1 (bsc_config.Kinv).
+ * Cell of a point.  The ingest's own: row = gs/2 - trunc(x/cs), col = gs/2 - trunc(y/cs), h = trunc(z/cs) - min_h, truncation
+ *   toward zero.  Along each axis truncation cell k therefore covers [k cs, (k+1) cs) for k > 0, (-cs, cs) for k = 0 (double
+ *   width) and ((k-1) cs, k cs] for k < 0, and the rays are walked through exactly these intervals on all three axes.  With an odd
+ *   grid_size row 0 / column 0 would be a second irregular cell: refused.
+ * Hit.  Among the stored voxels (id < max_id) with lo <= h <= hi (band_host; NULL or lo > hi: every height; clipped to
+ *   [0, max_h - min_h) like a band of bsc_topdown_slices) a voxel qualifies when the ray's parameter interval [t_in, t_out) through
+ *   its cell is not empty and meets [t_min, t_max]; the hit is the qualifying voxel with the smallest max(t_in, t_min).  A camera
+ *   inside an occupied voxel hits it at t_min.
+ *   voxel_dev[v, y, x]    the voxel's id as in occupied_ids; -1 for none
+ *   depth_dev[v, y, x]    max(t_in, t_min), computed in f64 and rounded once to f32; 0 for none, like an invalid depth pixel
+ *   rgb_dev[v, y, x, :]   grid_rgb[id] in RGB order; 0, 0, 0 for none
+ * The outputs are caller-owned device buffers; any may be NULL but not all three.  All three modes; an empty memory gives BSC_OK
+ * and -1 / 0 / 0.  The call first completes both library streams (the rgb chain writes colours on the side stream) and returns
+ * after its own work has completed; the result is bit-reproducible and does not depend on how the views are batched.  The resident
+ * cv_map / max_height and the results of the last localize call are untouched.  The occupancy bits the kernels walk (one 64-bit
+ * word per 4x4x4 brick, ceil(gs/4)^2 * ceil((max_h - min_h)/4) * 8 bytes, built once per call) are scratch of the context.
+ * BSC_E_INVALID, nothing written: a NULL context or transforms_host, n_views outside 1..1024, height or width outside 1..4096,
+ * all outputs NULL, a non-finite entry in a transform or in kinv_host, a kinv_host whose last row is not [0, 0, 1],
+ * not 0 <= t_min < t_max or a non-finite bound, an odd grid_size. */
+bsc_status bsc_render_views(bsc_ctx *ctx, int32_t n_views, const double *transforms_host /* (V,16) */,
+                            const double *kinv_host /* 9, or NULL: the context's own K^-1 */, int32_t height, int32_t width,
+                            double t_min, double t_max, const bsc_band *band_host /* one band or NULL */,
+                            int32_t *voxel_dev /* (V,H,W) */, float *depth_dev /* (V,H,W) */, uint8_t *rgb_dev /* (V,H,W,3) */);
+
 /* GESObjectNavRobot.weighted_cluster_centers (BSCAgent.py:479-497), the consumer of voxel_localized's output:
  * DBSCAN(eps, min_samples) over K top-ranked positions (scikit-learn semantics), similarity-weighted centres,
  * clusters ordered by mean similarity (stable, descending).  pos_host (K,3) / sim_host (K) NULL = cluster the first K
