@@ -109,6 +109,7 @@ struct bsc_ctx {
     // depth range (min_depth, max_depth) spans fewer than 2^28 values (BSC_REC12=1 keeps the 12-byte {alpha, rgb} records)
     bool rec8_ok;
     uint32_t rec8_zbase;       // bits of the largest float <= min_depth
+    uint32_t dbg_paths;        // BSC_DEBUG: the {fast, plain, rec8} choices of ingest_front_end already reported on stderr
     uint8_t *pat_x, *pat_y;   // (W), (H): patch column / row of a pixel column / row, 255 = outside the patch grid
     double *exp_tab;          // 64 x (hi, lo) of 2^(j/64): the table of bsc_exp (geometry_dev.h)
     // patch-aligned pair tiles (dense.hip): pixel rectangle {x0, width, y0, pixels} of every patch and the start of its

@@ -1896,6 +1896,15 @@ static bsc_status ingest_front_end(const IngestCall &c, const float *depth, cons
     // 8-byte records {rgb, index in block, depth offset} where the depth range allows (bsc_create), alpha left to the rgb chain
     const bool rec8 = gc.fast && plain && x->rec8_ok;
     S.rec8 = rec8;
+    {   // BSC_DEBUG: which k_points / chain forms this context takes, one line per distinct choice (host side only)
+        static const bool debug = getenv("BSC_DEBUG") != nullptr;
+        const uint32_t choice = 1u << ((int)gc.fast | (int)plain << 1 | (int)rec8 << 2);
+        if (debug && !(x->dbg_paths & choice)) {
+            x->dbg_paths |= choice;
+            fprintf(stderr, "bsc_ingest: k_points fast=%d plain=%d rec8=%d group_rpw=%d\n", (int)gc.fast, (int)plain, (int)rec8,
+                    x->group_rpw);
+        }
+    }
 #define BSC_LAUNCH_POINTS_R(FASTV, PLAINV, R8)                                                                                 \
     do {                                                                                                                       \
         if (x->group_rpw == 16) BSC_LAUNCH_POINTS(FASTV, 16, PLAINV, R8);                                                      \

@@ -417,7 +417,10 @@ def test_chain_and_order_knobs_keep_the_result(knob):
     right behind its order stage, no hot split, 8-wavefront hot tiles, other length classes, 1024-point blocks; round 6: the long
     chain as one launch, 16-wavefront hot tiles, block scans + totals as separate launches, scalars by copy instead of the host
     mailbox, source pixel by division, 12-byte records, rocPRIM sorts) — never the result: the long-chain scene in three calls, bit-exact against the oracle, under each of them.  Most are read once per
-    process, so every case runs in its own interpreter."""
+    process, so every case runs in its own interpreter.
+    _dense_vs_oracle passes a host alpha, which switches PLAIN and the 8-byte records off (ingest_front_end): every case here runs
+    the 12-byte-record kernels, and BSC_REC12=1 compares that path with itself.  The kernels of the default path (no alpha passed)
+    are held to the oracle under these knobs by tests/test_gpu_chain_ladder.py."""
     import os, subprocess, sys
     name, val = knob.split("=")
     code = ("import sys; sys.path[:0] = ['.', 'tests', 'tests/golden']; import test_gpu_edges as t; "
