@@ -4,8 +4,10 @@
 // GEMM of the vendor library runs ~115 TFLOP/s; the 16-bit MFMA peaks at 2.5 PFLOP/s.  An f32 value is, to 22 significant bits,
 // the sum of two fp16 pieces  h = fp16(x), l = fp16(x - h)  (the difference is exact in f32; both roundings to nearest), so
 //     x w = xh wh + xh wl + xl wh + O(2^-22 |x w|)
-// and the three piece products are exact in the matrix core's f32 accumulator: three v_mfma_f32_32x32x16_f16 per f32 product
-// term at 16x the f32 MFMA rate.  (Three bf16 pieces need six products for the same accuracy; with three products they leave
+// and the three piece products are exact in the matrix core's f32 accumulator: three fp16 MFMAs per f32 product term at 16x the f32
+// MFMA rate — v_mfma_f32_16x16x32_f16 in every tile whose weights arrive by DMA: the same work in twice as many instructions of half
+// the length as v_mfma_f32_32x32x16_f16, at which the chip holds a higher clock (profiles/README.md, "Split GEMM: 16x16x32 MFMAs at the same tile").
+// (Three bf16 pieces need six products for the same accuracy; with three products they leave
 // 2^-16 — k_cosine_bf16x3 of cosine_scan.hip is the six-product form.  fp16 pieces have a 5-bit exponent: the weights are scaled by
 // a power of two per matrix so that their largest element sits near 2^3, the activation operand by a per-layer power of two, and
 // the scales leave through the epilogue exactly; what remains of the narrow range is that the l piece of an element 2^10 below the
@@ -15,14 +17,16 @@
 //   C[m][n] = epilogue( out_scale * sum_k A[m][k] W[n][k] + bias[n] )        A (M,K) f32 row-major, W (N,K) as nn.Linear holds it
 //
 //   workgroup  256 rows of A x 256 rows of W, 8 wavefronts; wavefront w owns the 32 rows [32 w, 32 w + 32) of the tile
-//   A operand  straight from global memory in fragment layout — lane (i = lane & 31, g = lane >> 5) loads the 16 floats
-//              [32 c + 16 g, + 16) of its row (one 128-byte line per row and K chunk over the two lane groups) and splits
-//              them in registers (v_cvt_pk_f16_f32);
+//   A operand  straight from global memory in fragment layout — lane (i = lane & 15, g = lane >> 4) loads the 8 floats
+//              [32 c + 8 g, + 8) of rows i and i + 16 of its wavefront's 32 (one 128-byte line per row and K chunk over the four
+//              lane groups) and splits them in registers (v_cvt_pk_f16_f32); a uniform base + a 32-bit offset per lane and row;
 //   W operand  pieces precomputed once per weight matrix (bsc_enc_split_weights: planes h, l of (N,K) fp16), one 32-wide K chunk
 //              at a time from global memory straight into LDS (global_load_lds_dwordx4: no register stage), double-buffered;
-//              64-byte rows whose 16-byte columns are XOR-swizzled on the SOURCE address (conflict-free 16-byte reads);
-//   MFMA       the weights are the FIRST operand (D' = W X^T), so a lane of the accumulator tile holds ONE row of C and four
-//              consecutive columns per register quad;
+//              64-byte rows whose 16-byte columns are XOR-swizzled on the SOURCE address (conflict-free 16-byte reads of 16 rows x
+//              4 columns: gs_w_swz of gemm_split_plan.h, where all lane -> address maps of this loop live);
+//   MFMA       a chunk is ONE K step: per wavefront 16 column tiles of 16 x 2 row halves x 3 products = 96 MFMAs, 32 ds_read_b128.
+//              The weights are the FIRST operand (D' = W X^T), so a lane of an accumulator tile holds ONE row of C and four
+//              consecutive columns; 2 x 16 tiles of four registers = 128 accumulator registers;
 //   epilogue   bias, bias + GELU(tanh), bias + residual (C may alias the residual) — nothing elementwise is left between GEMMs.
 //              Each wavefront turns its 32 x 32 tiles round in 4 KB of LDS of its own and moves them as whole 128-byte lines
 //              (f32 rows or piece chunks), the residual rows requested right before the tile that adds them.
@@ -30,7 +34,7 @@
 // A tile is fetched into that XCD's L2 once.
 #include "bsc_internal.h"
 #include "att_ticket.h"
-#include "gemm_split_plan.h"          // GS_KC, GS_PITCH, the epilogue / operand mode ids, the launch plan and gs_tile_of
+#include "gemm_split_plan.h"          // GS_KC, GS_PITCH, the epilogue / operand mode ids, the launch plan, gs_tile_of, the fragment maps
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
@@ -300,8 +304,8 @@ __global__ __launch_bounds__(GS_TPB) void k_split_rows(const float *__restrict__
     *(uint2 *)(o + 32) = make_uint2(l0, l1);
 }
 
-// Workgroup tile (WR * MR * 32) rows x (WC * NT * 32) columns; wavefront (wr, wc) owns MR row fragments x NT column tiles:
-// every weight fragment read from LDS feeds MR * 3 MFMAs, every activation fragment NT * 3.
+// Workgroup tile (WR * MR * 32) rows x (WC * NT * 32) columns; wavefront (wr, wc) owns MR row fragments of 32 x NT column tiles of 32
+// (as 2 row halves x 2 NT tiles of 16 where the MFMA is 16x16x32): every weight fragment read from LDS feeds MR * 3 MFMAs per row half.
 // APIECES: A comes as P32 pieces (made by the producing kernel) — otherwise as f32 rows, split in registers.
 // CPIECES: C leaves as P32 pieces scaled by c_scale (the hidden tensor of the MLP: read by the next GEMM only).
 // One tile of a persistent workgroup.  primed: the first two A chunks (xf, xg) and the first weight chunk (LDS buffer `par`) were
@@ -341,9 +345,18 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     constexpr int NTHR = 64 * WR * WC;
     constexpr int NLD = 2 * WROWS * 4 / NTHR;                                 // 16-byte pieces of a weight chunk per thread
     // (the wavefront's index as a scalar: its rows, LDS blocks and strips are then scalar arithmetic, not registers per lane)
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // (The thread index goes through an opaque copy per tile: what a tile derives from it per lane — fragment rows, LDS offsets — is a few
+    //  instructions, but values of that kind that the compiler computes once for the whole persistent loop stay live across every
+    //  chunk loop and end up in scratch.)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = w / WC, wc = w - wr * WC;
-    const int i = lane & 31, g = lane >> 5;
+    // Fragment layout of a lane.  DMA tiles (v_mfma_f32_16x16x32_f16): i = lane & 15, g = lane >> 4 — rows i and i + 16 of the wavefront's
+    // 32 (RH = 2 row halves), the eight k [8 g, 8 g + 8) of a chunk.  DEEP (v_mfma_f32_32x32x16_f16, two sub-steps per chunk): row
+    // i = lane & 31, the sixteen k [16 g, 16 g + 16), g = lane >> 5.
+    constexpr int RH = DEEP ? 1 : 2, GK = DEEP ? 16 : 8;
+    const int i = DEEP ? lane & 31 : gs_acc_row(lane, 0), g = DEEP ? lane >> 5 : lane >> 4;
 #ifdef BSC_GEMM_PROFILE
     if (threadIdx.x == 0 && prof_idx < GS_PROF_MAX) {
         uint32_t hw;
@@ -355,54 +368,81 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     GS_T(1);
 #endif
     const int64_t row0 = tm * TROWS + wr * (MR * 32);
-    // per-lane row base: f32 rows (16 floats of the chunk per lane) or P32 pieces (8 halfs of either piece per sub-step)
-    auto row_base = [&](int64_t first_row, int mr) {
-        const int64_t row = first_row + mr * 32 + i;
-        const int64_t rc = row < M ? row : M - 1;                           // clamped: padded rows are not stored
-        // lane group g contracts k = 16 g + 8 sstep + (0..7) of the chunk in sub-step sstep — the same split of the 32 on both operands
-        return APIECES ? (const char *)((const uint16_t *)Av + rc * 2 * k_full + g * 16) : (const char *)((const float *)Av + rc * k_full + g * 16);
+    // A rows: a uniform base (the wavefront's first row, clamped to the matrix) + one 32-bit byte offset per lane and row — f32 rows
+    // (GK floats of the chunk per lane and row) or P32 pieces (GK halfs of either piece); a row is 4 k_full bytes in both forms.
+    // Rows past M read row M - 1 (padded rows are not stored).  Lane group g contracts k = GK g + (0 .. GK - 1) of the chunk — the same
+    // split of the 32 on both operands.
+    // (Rows are counted from the wavefront's first one in 32 bits — rows_left of them exist, a uniform number —: 64-bit row numbers per
+    //  lane cost the loop's register budget several registers for values like i | 16.)
+    auto tile_base = [&](int64_t first_row) { return (const char *)Av + (first_row < M ? first_row : M - 1) * 4 * k_full; };
+    auto rows_left = [&](int64_t first_row) { return (int)(M - first_row < MR * 32 ? M - first_row : MR * 32); };         // <= 0: none
+    auto row_off = [&](int64_t first_row, int mr, int rh) {
+        const int lr = mr * 32 + 16 * rh + i, left = rows_left(first_row);
+        const int dr = left > 0 ? (lr < left ? lr : left - 1) : 0;
+        return (uint32_t)(dr * 4 * k_full + g * GK * (APIECES ? 2 : 4));
     };
-    const char *arow[MR];
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr) arow[mr] = row_base(row0, mr);
-    // LayerNorm constants of the lane's rows (one record per row; the tile with n0 == 0 leaves the means for the next producer)
-    float ln_m[MR], ln_rs[MR];
-    if constexpr (AMODE == GS_A_LN) {
-#pragma unroll
-        for (int mr = 0; mr < MR; ++mr) {
-            const int64_t row = row0 + mr * 32 + i;
-            const f32x4_t *rec = (const f32x4_t *)(ln_stats + (row < M ? row : M - 1) * GS_LN_REC);
-            const f32x4_t r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3], r4 = rec[4];
-            const float sa = ((r0[2] + r1[0]) + (r1[2] + r2[0])) + ((r2[2] + r3[0]) + (r3[2] + r4[0]));
-            const float sb = ((r0[3] + r1[1]) + (r1[3] + r2[1])) + ((r2[3] + r3[1]) + (r3[3] + r4[1]));
-            const float inv_w = 1.0f / (float)K, da = sa * inv_w;
-            ln_m[mr] = r0[0] + da;
-            ln_rs[mr] = 1.0f / sqrtf(fmaxf(sb * inv_w - da * da, 0.f) + ln_eps);
-            if (n0 == 0 && wc == 0 && g == 0 && row < M) ln_mu[row] = ln_m[mr];
-        }
-    }
-    const int nchunks = K / GS_KC;
-    has_next = has_next && nchunks >= 2;
-    f32x16 acc[MR][NT];
+    const char *const abase = tile_base(row0);
+    uint32_t arow[MR][RH];
 #pragma unroll
     for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
-        for (int t = 0; t < NT; ++t)
+        for (int rh = 0; rh < RH; ++rh) arow[mr][rh] = row_off(row0, mr, rh);
+    // LayerNorm constants of the lane's rows (one record per row).  The tile with n0 == 0 leaves the means for the next producer: of
+    // the four lanes g = 0 .. 3 that hold a row, lane g == 0 writes it — each of its RH rows, so every row below M exactly once.
+    float ln_m[MR * RH], ln_rs[MR * RH];
+    if constexpr (AMODE == GS_A_LN) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mr][t][r] = 0.f;
+        for (int mr = 0; mr < MR * RH; ++mr) {
+            const int lr = (mr / RH) * 32 + 16 * (mr % RH) + i, left = rows_left(row0);
+            // (uniform base + a 32-bit offset per lane: no 64-bit address arithmetic per lane)
+            const char *recb = (const char *)(ln_stats + (left > 0 ? row0 : M - 1) * GS_LN_REC);
+            const f32x4_t *rec = (const f32x4_t *)(recb + (uint32_t)((left > 0 ? (lr < left ? lr : left - 1) : 0) * (GS_LN_REC * 4)));
+            const f32x4_t r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3], r4 = rec[4];
+            const float sa = ((r0[2] + r1[0]) + (r1[2] + r2[0])) + ((r2[2] + r3[0]) + (r3[2] + r4[0]));
+            const float sb = ((r0[3] + r1[1]) + (r1[3] + r2[1])) + ((r2[3] + r3[1]) + (r3[3] + r4[1]));
+            const float inv_w = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(1.0f / (float)K))), da = sa * inv_w;     // (a scalar)
+            ln_m[mr] = r0[0] + da;
+            ln_rs[mr] = 1.0f / sqrtf(fmaxf(sb * inv_w - da * da, 0.f) + ln_eps);
+            if (n0 == 0 && wc == 0 && g == 0 && lr < left) *(float *)((char *)(ln_mu + row0) + (uint32_t)(4 * lr)) = ln_m[mr];
+        }
+    }
+    const int nchunks = K / GS_KC;
+    // (gs_plan admits whole chunks only.  Told so, the compiler drops the path round the chunk loop — on which the prefetch registers
+    //  would pass unchanged, and for which it kept a second copy of them in scratch across the loop.)
+    __builtin_assume(nchunks >= 1);
+    has_next = has_next && nchunks >= 2;
+    // accumulators: DMA tiles acc[mr][row half][16-column tile] (four registers each), DEEP acc32[mr][32-column tile] (sixteen) —
+    // MR NT 16 registers either way; the array of the other form is empty in effect (never touched)
+    f32x4_t acc[MR][2][DEEP ? 1 : 2 * NT];
+    f32x16 acc32[MR][DEEP ? NT : 1];
+#pragma unroll
+    for (int mr = 0; mr < MR; ++mr) {
+        if constexpr (DEEP) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc32[mr][t][r] = 0.f;
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4 * NT; ++t) acc[mr][t / (2 * NT)][t % (2 * NT)] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+    }
     // prefetch registers as first-class vector values (an array that is live across the chunk loop would be left in scratch):
     // xf = the A chunk about to be used, xg = the one after it (two chunks of load latency hidden)
     typedef typename gs_xf<MR>::type xf_t;
     typedef uint32_t qr_t __attribute__((ext_vector_type(4 * NLD)));
     qr_t qr;
-    auto load_a = [&](xf_t &xf, const char *const (&ar)[MR], int c) {
+    auto load_a = [&](xf_t &xf, const char *ab, const uint32_t (&ar)[MR][RH], int c) {
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
             for (int v4 = 0; v4 < 4; ++v4) {
-                // f32: floats [4 v4, 4 v4 + 4) of the lane's 16; pieces: v4 = 2 piece + sub-step -> halfs [16 g + 8 sstep, + 8) of the piece
-                const uint4 v = APIECES ? *(const uint4 *)(ar[mr] + (int64_t)c * 128 + (v4 >> 1) * 64 + (v4 & 1) * 16)
-                                        : *(const uint4 *)(ar[mr] + (int64_t)c * 128 + 16 * v4);
+                // DEEP  f32: floats [4 v4, 4 v4 + 4) of the lane's 16; pieces: v4 = 2 piece + sub-step -> halfs [16 g + 8 sstep, + 8) of the piece
+                // else  f32: v4 = 2 row half + x -> floats [4 x, 4 x + 4) of the row's 8; pieces: v4 = 2 piece + row half -> the 16 bytes at
+                //       16 g (h) or 64 + 16 g (l) of the row's chunk block.  Four 16-byte loads per chunk and mr in every form.
+                const uint32_t ro = DEEP ? ar[mr][0] : ar[mr][(APIECES ? v4 & 1 : v4 >> 1) % RH];
+                const int cb = DEEP ? (APIECES ? (v4 >> 1) * 64 + (v4 & 1) * 16 : 16 * v4) : APIECES ? (v4 >> 1) * 64 : (v4 & 1) * 16;
+                const uint4 v = *(const uint4 *)(ab + (int64_t)c * 128 + cb + (size_t)ro);
                 xf[16 * mr + 4 * v4] = v.x; xf[16 * mr + 4 * v4 + 1] = v.y; xf[16 * mr + 4 * v4 + 2] = v.z; xf[16 * mr + 4 * v4 + 3] = v.w;
             }
     };
@@ -414,18 +454,19 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // pointer per j in registers — and, in the persistent form of this kernel, in scratch.)
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void *)Wp, 0, (int)(4 * w_plane), 0x00020000);
     // DMA form: a wavefront's instruction moves 16 rows x 64 bytes, which land in lane order — LDS slot (row, c'), c' the 16-byte
-    // column, holds global column c' ^ ((row >> 2) & 3) (the swizzle is on the source address; PR is a multiple of 16, so it is the
-    // same for every j).  The fragment reads below apply the same XOR: 16 consecutive lanes read rows r .. r + 15 at column cc, i.e.
-    // the 16-byte bank slots 4 (row & 3) + (cc ^ (row >> 2 & 3)) — 16 different ones of the 16.
-    const int wthr = ((tid >> 2) * k_full + (DEEP ? tid & 3 : (tid & 3) ^ ((tid >> 4) & 3)) * 8) * 2;
+    // column, holds global column gs_w_col(row, c') (the swizzle is on the source address; PR is a multiple of 16, so it is the
+    // same for every j).  The fragment reads below go through the same function (gs_frag_off); gemm_split_plan.h derives the swizzle
+    // from the lane groups of a 16-byte LDS read.
+    static_assert(DEEP || (PR % 16 == 0 && NLD == gs_dma_count(WROWS, NTHR) && BUF * 2 == gs_w_buf_bytes(WROWS)), "DMA plan");
+    const int wthr = ((tid >> 2) * k_full + (DEEP ? tid & 3 : gs_dma_src_col(tid)) * 8) * 2;
     const int lthr = (tid >> 2) * GS_PITCH + (tid & 3) * 8;
-    const uint32_t ws_m0 = gs_lds_addr((const char *)Ws + w * 1024);        // where the wavefront's 16 rows of piece j = 0 land
+    const uint32_t ws_m0 = gs_lds_addr((const char *)Ws + gs_dma_lds_off(WROWS, NTHR, 0, 0, w));      // where the wavefront's 16 rows of piece j = 0 land
     auto dma_w = [&](int buf, int nbase, int c) {
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             // (the uniform part of the address fits 32 bits — the planes of one matrix — and is made a scalar by hand)
             const int uni = (int)(((int64_t)(j / PPP) * w_plane + (int64_t)(nbase + (j % PPP) * PR) * k_full + c * GS_KC) * 2);
-            gs_dma16((const char *)Wp + (uint32_t)__builtin_amdgcn_readfirstlane(uni), (uint32_t)wthr, ws_m0 + (uint32_t)(buf * BUF + ((j / PPP) * WROWS + (j % PPP) * PR) * PITCH) * 2);
+            gs_dma16((const char *)Wp + (uint32_t)__builtin_amdgcn_readfirstlane(uni), (uint32_t)wthr, ws_m0 + (uint32_t)gs_dma_lds_off(WROWS, NTHR, buf, j, 0));
         }
     };
     // the register-staged form (the few-rows tile): global -> registers (load_w), registers -> LDS a chunk later (store_w)
@@ -450,14 +491,14 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     qr_t qr2;
     if (!primed) {
         if constexpr (DEEP) {
-            load_a(xf, arow, 0);
+            load_a(xf, abase, arow, 0);
             load_w(qr, n0, 0);
-            if (nchunks > 1) { load_a(xg, arow, 1); load_w(qr2, n0, 1); }
+            if (nchunks > 1) { load_a(xg, abase, arow, 1); load_w(qr2, n0, 1); }
             store_w(qr, par);
         } else {
             dma_w(par, n0, 0);
-            load_a(xf, arow, 0);
-            if (nchunks > 1) load_a(xg, arow, 1);
+            load_a(xf, abase, arow, 0);
+            if (nchunks > 1) load_a(xg, abase, arow, 1);
             gs_wait_vm<0>();
         }
         __syncthreads();
@@ -465,7 +506,7 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     GS_T(2);
     auto chunk_body = [&](const int c, qr_t &q_load, qr_t &q_store) __attribute__((always_inline)) {
         const int buf = (c + par) & 1;
-        // this chunk's rows as fp16 pieces (two sub-steps of 8 halfs), then the next chunk's loads go in flight
+        // this chunk's rows as fp16 pieces — [mr][row half] of 8 halfs (DEEP: [mr][sub-step]) —, then the next chunk's loads go in flight
         uint32_t ah[MR][2][4], al[MR][2][4];
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr) {
@@ -482,7 +523,8 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                     f32x2_t p0 = {__uint_as_float(xf[16 * mr + 4 * v4]), __uint_as_float(xf[16 * mr + 4 * v4 + 1])};
                     f32x2_t p1 = {__uint_as_float(xf[16 * mr + 4 * v4 + 2]), __uint_as_float(xf[16 * mr + 4 * v4 + 3])};
                     if constexpr (AMODE == GS_A_LN) {
-                        const f32x2_t mm = {ln_m[mr], ln_m[mr]}, rr = {ln_rs[mr], ln_rs[mr]};
+                        const int lr = mr * RH + (v4 >> 1) % RH;            // the row the four floats belong to
+                        const f32x2_t mm = {ln_m[lr], ln_m[lr]}, rr = {ln_rs[lr], ln_rs[lr]};
                         p0 = (p0 - mm) * rr;
                         p1 = (p1 - mm) * rr;
                     } else {
@@ -503,46 +545,89 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
         if constexpr (DEEP) {
             // unconditional requests (the last two iterations repeat the last chunk): behind a branch the compiler cannot count on the
             // younger loads being in flight and makes the LDS stores below wait for everything
-            load_a(xg, arow, a_next ? nchunks - 1 : c + 2);
+            load_a(xg, abase, arow, a_next ? nchunks - 1 : c + 2);
             load_w(q_load, n0, a_next ? nchunks - 1 : c + 2);
         } else {
             // Issue order of a chunk: the next weight chunk's DMA, then the A loads.  The wait at the chunk's end then leaves exactly the
             // A loads in flight, and the DMAs — older than those — add nothing to the compiler's own count for them.
             if (w_req) dma_w(buf ^ 1, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
             if (a_req) {
-                const char *ap[MR];
+                const int64_t nrow0 = next_tm * TROWS + wr * (MR * 32);
+                uint32_t ap[MR][RH];
 #pragma unroll
-                for (int mr = 0; mr < MR; ++mr) ap[mr] = a_next ? row_base(next_tm * TROWS + wr * (MR * 32), mr) : arow[mr];
-                load_a(xg, ap, a_next ? c + 2 - nchunks : c + 2);
+                for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+                    for (int rh = 0; rh < RH; ++rh) ap[mr][rh] = a_next ? row_off(nrow0, mr, rh) : arow[mr][rh];
+                load_a(xg, a_next ? tile_base(nrow0) : abase, ap, a_next ? c + 2 - nchunks : c + 2);
             }
         }
-        // the lane's 16-byte column of sub-step sstep is 2 g + sstep; swizzled rows hold it at (2 g + sstep) ^ ((row >> 2) & 3)
-        const uint16_t *wrow = &Ws[buf * BUF + (wc * NT * 32 + i) * PITCH];
-        const uint16_t *wbs[2] = {wrow + (DEEP ? g * 16 : ((2 * g) ^ ((i >> 2) & 3)) * 8), wrow + (DEEP ? g * 16 + 8 : ((2 * g + 1) ^ ((i >> 2) & 3)) * 8)};
+        if constexpr (DEEP) {
+            // The few-rows tile keeps v_mfma_f32_32x32x16_f16: six MFMAs per chunk between two barriers — it turns on the latency of
+            // its LDS round trip, not on the clock the matrix pipe holds, and no encoder forward of many frames runs it.  Its rows are
+            // register-staged at pitch GS_PITCH (no swizzle); the lane's 16-byte column of sub-step sstep is 2 g + sstep.
+            const uint16_t *wrow = &Ws[buf * BUF + (wc * NT * 32 + i) * PITCH];
 #pragma unroll
-        for (int sstep = 0; sstep < 2; ++sstep) {
-            // one piece of the weights at a time; smallest terms first; consecutive MFMAs go to different accumulators
-            const uint16_t *wb = wbs[sstep];
-            half8_t wf[NT];
+            for (int sstep = 0; sstep < 2; ++sstep) {
+                // one piece of the weights at a time; smallest terms first; consecutive MFMAs go to different accumulators
+                const uint16_t *wb = wrow + g * 16 + 8 * sstep;
+                half8_t wf[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) wf[t] = *(const half8_t *)(wb + (1 * WROWS + t * 32) * PITCH);
+                for (int t = 0; t < NT; ++t) wf[t] = *(const half8_t *)(wb + (1 * WROWS + t * 32) * PITCH);
 #pragma unroll
-            for (int mr = 0; mr < MR; ++mr)
+                for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    acc[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)ah[mr][sstep], acc[mr][t], 0, 0, 0);     // h l
+                    for (int t = 0; t < NT; ++t)
+                        acc32[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)ah[mr][sstep], acc32[mr][t], 0, 0, 0);     // h l
 #pragma unroll
-            for (int t = 0; t < NT; ++t) wf[t] = *(const half8_t *)(wb + (0 * WROWS + t * 32) * PITCH);
+                for (int t = 0; t < NT; ++t) wf[t] = *(const half8_t *)(wb + (0 * WROWS + t * 32) * PITCH);
 #pragma unroll
-            for (int mr = 0; mr < MR; ++mr)
+                for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    acc[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)al[mr][sstep], acc[mr][t], 0, 0, 0);     // l h
+                    for (int t = 0; t < NT; ++t)
+                        acc32[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)al[mr][sstep], acc32[mr][t], 0, 0, 0);     // l h
 #pragma unroll
-            for (int mr = 0; mr < MR; ++mr)
+                for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    acc[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)ah[mr][sstep], acc[mr][t], 0, 0, 0);     // h h
+                    for (int t = 0; t < NT; ++t)
+                        acc32[mr][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t], *(const half8_t *)ah[mr][sstep], acc32[mr][t], 0, 0, 0);     // h h
+            }
+        } else {
+            // A chunk is ONE K step of v_mfma_f32_16x16x32_f16: 2 NT column tiles of 16 x 2 row halves x 3 piece products.  The weight
+            // fragments of a piece are read in batches of TB tiles (all 16 of a 256-column strip at once would be 64 registers); every
+            // fragment feeds MR * 2 MFMAs per product, every activation fragment 2 NT.  One piece of the weights at a time; smallest terms
+            // first (h l, l h, h h per accumulator); consecutive MFMAs go to different accumulators.
+            constexpr int TB = 2 * NT < 8 ? 2 * NT : 8;
+            static_assert((2 * NT) % TB == 0, "column tiles per wavefront: whole batches");
+            const char *wb = (const char *)Ws + gs_frag_off(WROWS, 0, 0, wc * NT * 32, 0, lane) + buf * (BUF * 2);
+#pragma unroll
+            for (int b = 0; b < 2 * NT / TB; ++b) {
+                half8_t wf[TB];
+#pragma unroll
+                for (int t = 0; t < TB; ++t) wf[t] = *(const half8_t *)(wb + gs_frag_off(WROWS, 0, 1, 0, b * TB + t, 0));
+#pragma unroll
+                for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+                    for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+                        for (int t = 0; t < TB; ++t)
+                            acc[mr][rh][b * TB + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[t], *(const half8_t *)ah[mr][rh], acc[mr][rh][b * TB + t], 0, 0, 0);     // h l
+#pragma unroll
+                for (int t = 0; t < TB; ++t) wf[t] = *(const half8_t *)(wb + gs_frag_off(WROWS, 0, 0, 0, b * TB + t, 0));
+#pragma unroll
+                for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+                    for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+                        for (int t = 0; t < TB; ++t)
+                            acc[mr][rh][b * TB + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[t], *(const half8_t *)al[mr][rh], acc[mr][rh][b * TB + t], 0, 0, 0);     // l h
+#pragma unroll
+                for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+                    for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+                        for (int t = 0; t < TB; ++t)
+                            acc[mr][rh][b * TB + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[t], *(const half8_t *)ah[mr][rh], acc[mr][rh][b * TB + t], 0, 0, 0);     // h h
+            }
         }
         if constexpr (DEEP) {
             if (c + 1 < nchunks) store_w(q_store, buf ^ 1);
@@ -568,9 +653,11 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     }
     par = (par + nchunks) & 1;
     GS_T(3);
-    // The weights are the MFMA's FIRST operand (D' = W X^T): lane (i, g) of accumulator tile (mr, t) holds ROW row0 + 32 mr + i of C
-    // and, in registers 4 q .. 4 q + 3, the four consecutive columns 32 t + 8 q + 4 g + (0..3) of the wavefront's strip.  A 32 x 32
-    // tile is 128 bytes per row either way (32 floats, or the P32 chunk [32 h | 32 l]): the wavefront turns it round in its own
+    // The weights are the MFMA's FIRST operand (D' = W X^T): a lane holds ROWS of C and four consecutive columns per register quad.
+    // DMA tiles: lane (i, g) of accumulator tile (mr, row half, t') holds row row0 + 32 mr + gs_acc_row and the columns gs_acc_col =
+    // 16 t' + 4 g + (0..3) of the wavefront's strip; the quad q = 2 row half + (t' & 1) of the 32-column tile t = t' >> 1 below.
+    // DEEP: lane (i, g) of tile (mr, t) holds row row0 + 32 mr + i and in registers 4 q .. 4 q + 3 the columns 32 t + 8 q + 4 g + (0..3).
+    // A 32 x 32 tile is 128 bytes per row either way (32 floats, or the P32 chunk [32 h | 32 l]): the wavefront turns it round in its own
     // 4 KB of LDS (the weight buffers are free after the loop's last barrier; no workgroup barrier here) and moves it as WHOLE
     // 128-byte lines — 8 lanes per row, 8 rows per 16-byte instruction.  How this epilogue got here (scripts/gemm_phase_profile.sh):
     // one 4-byte access per element in accumulator order was 15 us per tile for piece output (VALU: ~25 instructions per element)
@@ -582,14 +669,21 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // are worth more to the main loop than the prefetch is to the epilogue.  Prefetching one tile ahead through LDS instead (no register
     // held across the loop) was measured on top of the weight DMA and dropped: a proj tile's epilogue 14.3 -> 12.5 us, the forward at
     // 768 frames 88.6 -> 89.0 ms (profiles/README.md) — one tile of cover is less than the rows' HBM latency.
+    // The epilogue derives its per-lane values from a copy of the lane index that the compiler cannot see through: they depend on the
+    // lane and the tile only, so it would otherwise compute them ahead of the chunk loop and carry them across it in scratch.
+    int lane_e = lane;
+    asm volatile("" : "+v"(lane_e));
+    const int ie = lane_e & 31, ge = lane_e >> 5;                           // (DEEP) the lane's row and column group
     const bool full = row0 + MR * 32 <= M && n0 + WROWS <= N;               // (uniform) no bounds checks inside the tile
     float *C = (float *)Cv;
     uint16_t *Cp = (uint16_t *)Cv;
-    constexpr int EP = 136;                                                 // staged row pitch, bytes: conflict-free 8-byte writes
+    // staged row pitch, bytes: conflict-free 8-byte writes — a ds_write_b64 is served in groups of 16 consecutive lanes over 32 banks,
+    // and 16 consecutive rows at one column (either fragment layout) start at the dwords 34 row = 2 row (mod 32)
+    constexpr int EP = 136;
     constexpr int WLB = 32 * EP;                                            // per wavefront: one tile
     char *wl = epi_lds + w * WLB;                                           // beyond the weight buffers: the next tile's chunk 0 may sit there
     const float *bs = bias_lds + n0 + wc * NT * 32;                         // the bias values of the wavefront's column strip
-    const int rl = lane >> 3, seg = lane & 7;                               // line phase: row rl + 8 k of the tile, 16-byte segment seg
+    const int rl = lane_e >> 3, seg = lane_e & 7;                               // line phase: row rl + 8 k of the tile, 16-byte segment seg
     auto epilogue = [&](const bool chk) __attribute__((always_inline)) {
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr) {
@@ -624,22 +718,24 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                     if (EPI == GS_EPI_RESID) load_r(t);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const f32x4_t b4 = *(const f32x4_t *)&bs[32 * t + 8 * q + 4 * g];
+                        // the quad's row and first column within the 32 x 32 tile; its bias values are those of that column
+                        const int qrow = DEEP ? ie : gs_acc_row(lane_e, q >> 1), qcol = DEEP ? 8 * q + 4 * ge : gs_acc_col(lane_e, q & 1, 0);
+                        const f32x4_t b4 = *(const f32x4_t *)&bs[32 * t + qcol];
                         float v[4];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            v[e] = fmaf(acc[mr][t][4 * q + e], out_scale, b4[e]);
+                            v[e] = fmaf(DEEP ? acc32[mr][DEEP ? t : 0][4 * q + e] : acc[mr][q >> 1][DEEP ? 0 : 2 * t + (q & 1)][e], out_scale, b4[e]);
                             if (EPI == GS_EPI_GELU || EPI == GS_EPI_GELU_ERF) v[e] = gelu_of<EPI>(v[e]);
                         }
                         if (CPIECES) {
                             uint32_t h0, l0, h1, l1;
                             split2(v[0] * c_scale, v[1] * c_scale, h0, l0);
                             split2(v[2] * c_scale, v[3] * c_scale, h1, l1);
-                            *(uint2 *)(wl + i * EP + 16 * q + 8 * g) = make_uint2(h0, h1);
-                            *(uint2 *)(wl + i * EP + 64 + 16 * q + 8 * g) = make_uint2(l0, l1);
+                            *(uint2 *)(wl + qrow * EP + 2 * qcol) = make_uint2(h0, h1);
+                            *(uint2 *)(wl + qrow * EP + 64 + 2 * qcol) = make_uint2(l0, l1);
                         } else {
-                            *(float2 *)(wl + i * EP + 32 * q + 16 * g) = make_float2(v[0], v[1]);
-                            *(float2 *)(wl + i * EP + 32 * q + 16 * g + 8) = make_float2(v[2], v[3]);
+                            *(float2 *)(wl + qrow * EP + 4 * qcol) = make_float2(v[0], v[1]);
+                            *(float2 *)(wl + qrow * EP + 4 * qcol + 8) = make_float2(v[2], v[3]);
                         }
                     }
                     gs_wave_lds_order();
@@ -687,10 +783,11 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                 for (int t = 0; t < NT; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int64_t m = mbase + i;
-                        const int nl = 32 * t + 8 * (r >> 2) + 4 * g + (r & 3), n = n0 + wc * NT * 32 + nl;
+                        const int q = r >> 2;                               // the register's quad, as above
+                        const int64_t m = mbase + (DEEP ? ie : gs_acc_row(lane_e, q >> 1));
+                        const int nl = DEEP ? 32 * t + 8 * q + 4 * ge + (r & 3) : gs_acc_col(lane_e, 2 * t + (q & 1), r & 3), n = n0 + wc * NT * 32 + nl;
                         if (m >= M || n >= N) continue;
-                        float v = fmaf(acc[mr][t][r], out_scale, bs[nl]);
+                        float v = fmaf(DEEP ? acc32[mr][DEEP ? t : 0][r] : acc[mr][q >> 1][DEEP ? 0 : 2 * t + (q & 1)][r & 3], out_scale, bs[nl]);
                         if (EPI == GS_EPI_GELU || EPI == GS_EPI_GELU_ERF) v = gelu_of<EPI>(v);
                         if (EPI == GS_EPI_RESID) v += R[m * N + n];
                         C[m * N + n] = v;
@@ -746,13 +843,18 @@ __global__ __launch_bounds__(64 * WR * WC) void k_gemm_split(const void *__restr
         if (!cur.valid) { primed = false; continue; }
         const bool has_next = nxt.valid && nxt.half == cur.half && !(MR == 1 && NT == 1 && WR == 1);      // (the few-rows tile does not chain)
         const int prof_idx = (int)(qv * 8 + xcd);
+        // (gs_tile_of divides 64-bit numbers, which the vector unit does: its results are uniform but arrive in vector registers, and
+        //  every row number a tile derives from them would be 64-bit arithmetic per lane, live across the chunk loop.  Tile indices fit
+        //  32 bits: back to scalars by hand.)
+        const int64_t tm = __builtin_amdgcn_readfirstlane((int)cur.tm), next_tm = __builtin_amdgcn_readfirstlane((int)nxt.tm);
+        const int n0 = __builtin_amdgcn_readfirstlane(cur.n0), next_n0 = __builtin_amdgcn_readfirstlane(nxt.n0);
         if (!cur.half)
             gemm_split_tile<MR, NT, WR, WC, EPI, AMODE, CPIECES, STATS>(Ws, epi_lds, bias_lds, Av, M, K, Wp, w_plane, N, R, Cv, a_scale,
-                                                                        out_scale, c_scale, cur.tm, cur.n0, primed, has_next, nxt.tm, nxt.n0,
+                                                                        out_scale, c_scale, tm, n0, primed, has_next, next_tm, next_n0,
                                                                         par, xf, xg, prof_idx, ln_stats, ln_mu, ln_eps, k_full);
         else
             gemm_split_tile<MR, NH, WR, WC, EPI, AMODE, CPIECES, STATS>(Ws, epi_lds, bias_lds, Av, M, K, Wp, w_plane, N, R, Cv, a_scale,
-                                                                        out_scale, c_scale, cur.tm, cur.n0, primed, has_next, nxt.tm, nxt.n0,
+                                                                        out_scale, c_scale, tm, n0, primed, has_next, next_tm, next_n0,
                                                                         par, xf, xg, prof_idx, ln_stats, ln_mu, ln_eps, k_full);
         primed = has_next && K / GS_KC >= 2;
     }

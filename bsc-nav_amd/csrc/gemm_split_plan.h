@@ -1,6 +1,8 @@
 // gemm_split_plan.h — the launch plan of k_gemm_split (encoder_gemm.hip) as plain integer arithmetic: which tile, how the tiles are
-// dealt to the persistent workgroups, how many split-K slices, how much LDS.  No HIP header: tests/host/gemm_plan_main.cpp walks
-// the plans on the CPU.  gs_tile_of is the one definition of "which tile is entry qv of an XCD's list" — the kernel calls it too.
+// dealt to the persistent workgroups, how many split-K slices, how much LDS — and the lane -> address maps of its main loop (the
+// weight image in LDS, the MFMA fragments, the accumulator layout).  No HIP header: tests/host/gemm_plan_main.cpp walks the plans
+// on the CPU, tests/host/gemm_frag_main.cpp the maps.  gs_tile_of is the one definition of "which tile is entry qv of an XCD's
+// list", gs_dma_* / gs_frag_off / gs_acc_* of "which byte goes where" — the kernel calls them too.
 #pragma once
 #include <stdint.h>
 
@@ -52,6 +54,39 @@ GS_HD GsTile gs_tile_of(int n_tiles_n, int64_t n_tiles_m, int64_t q_full, int64_
     t.valid = qv < q_virtual && t.tm < n_tiles_m;
     return t;
 }
+
+// ---- the LDS weight image and the fragment maps of the DMA-scheduled tiles (every tile but the few-rows one) -----------------------
+// v_mfma_f32_16x16x32_f16 with the weights as the first operand (D' = W X^T): lane l = (i = l & 15, g = l >> 4) holds, of a 16-row
+// weight tile, row i and the chunk's halfs [8 g, 8 g + 8) — one 16-byte column of a 64-byte LDS row —, of the activations the same
+// eight k of rows i and i + 16 of the wavefront's 32, and of the accumulator tile (row half, tile) ROW 16 half + i of C and the four
+// consecutive columns 16 tile + 4 g + (0..3).  tests/host/gemm_frag_main.cpp composes these maps on the CPU; the kernel calls them.
+//
+// The image of a chunk: [2 buffers][2 pieces][wrows rows][4 columns of 16 bytes].  A DMA instruction of a wavefront lands in lane
+// order (16 rows x 64 bytes), so the swizzle is applied to the SOURCE column: slot (row, c) holds global column c ^ gs_w_swz(row).
+// A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32): four blocks
+// of four rows, two of them at g and two at g + 1.  A 256-byte bank window is four rows, so the four blocks must sit in four different
+// columns: with q = (row >> 2) & 3 the groups hold {q 0, 3 at g; q 1, 2 at g ^ 1} or {q 1, 2 at g; q 0, 3 at g ^ 1}, and
+// s = {0, 3, 2, 1} separates both (the plain s = q of the 32-row fragment of v_mfma_f32_32x32x16 does not: 0 ^ s[0] = 1 ^ s[1]).
+GS_HD constexpr int gs_w_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
+GS_HD constexpr int gs_w_col(int row, int c) { return c ^ gs_w_swz(row); }         // slot -> global column and back (an involution)
+// DMA plan of a workgroup of nthr threads for a chunk of wrows rows per piece: instruction j of thread tid moves 16 bytes
+GS_HD constexpr int gs_dma_count(int wrows, int nthr) { return 2 * wrows * 4 / nthr; }
+GS_HD constexpr int gs_dma_piece(int wrows, int nthr, int j) { return j / (wrows / (nthr / 4)); }
+GS_HD constexpr int gs_dma_row(int wrows, int nthr, int j, int tid) { return (j % (wrows / (nthr / 4))) * (nthr / 4) + (tid >> 2); }
+GS_HD constexpr int gs_dma_src_col(int tid) { return gs_w_col(tid >> 2, tid & 3); }                  // (nthr / 4 is a multiple of 16)
+// byte offsets into the image: where instruction j of a WAVEFRONT's lane 0 lands (lane l: + 16 l), and what a lane reads
+GS_HD constexpr int gs_w_buf_bytes(int wrows) { return 2 * wrows * GS_KC * 2; }
+GS_HD constexpr int gs_dma_lds_off(int wrows, int nthr, int buf, int j, int wave)
+{
+    return buf * gs_w_buf_bytes(wrows) + (gs_dma_piece(wrows, nthr, j) * wrows + gs_dma_row(wrows, nthr, j, 64 * wave)) * (GS_KC * 2);
+}
+GS_HD constexpr int gs_frag_off(int wrows, int buf, int piece, int strip_row0, int tile, int lane)
+{
+    return buf * gs_w_buf_bytes(wrows) + (piece * wrows + strip_row0 + 16 * tile + (lane & 15)) * (GS_KC * 2) + 16 * gs_w_col(lane & 15, lane >> 4);
+}
+// accumulator register r of tile (half, tile) of lane -> (row, column) of the wavefront's 32 x NT 32 strip
+GS_HD constexpr int gs_acc_row(int lane, int half) { return 16 * half + (lane & 15); }
+GS_HD constexpr int gs_acc_col(int lane, int tile, int r) { return 16 * tile + 4 * (lane >> 4) + r; }
 
 // The plan of C (M, N) = A (M, K) W^T.  c_pieces: C leaves as pieces; ln_bufs: the caller gave both LayerNorm buffers (statistics
 // records and means); stats: the residual epilogue leaves the row statistics; ws_bytes: the caller's workspace for split-K partial
