@@ -313,6 +313,7 @@ __global__ __launch_bounds__(GS_TPB) void k_split_rows(const float *__restrict__
 // the same shape — so that a workgroup's tiles form one continuous stream of chunks and only its first tile pays the latency of
 // a prologue.  par: parity of the LDS buffer that holds chunk 0 (advances by the chunk count per tile).
 template <int MR> struct gs_xf { typedef uint32_t type __attribute__((ext_vector_type(16 * MR))); };
+template <bool B> struct gs_flag { static constexpr bool value = B; };
 // AMODE: how the activation operand arrives — GS_A_F32 f32 rows (split in registers), GS_A_PIECES P32 pieces, GS_A_LN f32 rows of
 // the residual stream that are LayerNorm'd while they are split: y = (x - mean) * rstd per row (gamma is folded into the weight
 // columns and beta into the bias by the host, once per matrix), mean / rstd from the row's statistics record (below).
@@ -504,43 +505,70 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
         __syncthreads();
     }
     GS_T(2);
-    auto chunk_body = [&](const int c, qr_t &q_load, qr_t &q_store) __attribute__((always_inline)) {
+    // f32 rows -> fp16 pieces of one chunk: h[mr][row half] / l[mr][row half] of 8 halfs (DEEP: [mr][sub-step])
+    auto split_a = [&](const xf_t &x, uint32_t (&h)[MR][2][4], uint32_t (&l)[MR][2][4]) {
+#pragma unroll
+        for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+            for (int v4 = 0; v4 < 4; ++v4) {
+                // pairs through the packed f32 instructions (v_pk_add_f32 / v_pk_mul_f32): half the vector issue slots
+                f32x2_t p0 = {__uint_as_float(x[16 * mr + 4 * v4]), __uint_as_float(x[16 * mr + 4 * v4 + 1])};
+                f32x2_t p1 = {__uint_as_float(x[16 * mr + 4 * v4 + 2]), __uint_as_float(x[16 * mr + 4 * v4 + 3])};
+                if constexpr (AMODE == GS_A_LN) {
+                    const int lr = mr * RH + (v4 >> 1) % RH;            // the row the four floats belong to
+                    const f32x2_t mm = {ln_m[lr], ln_m[lr]}, rr = {ln_rs[lr], ln_rs[lr]};
+                    p0 = (p0 - mm) * rr;
+                    p1 = (p1 - mm) * rr;
+                } else {
+                    const f32x2_t ss = {a_scale, a_scale};
+                    p0 *= ss;
+                    p1 *= ss;
+                }
+                split2v(p0, h[mr][v4 >> 1][2 * (v4 & 1)], l[mr][v4 >> 1][2 * (v4 & 1)]);
+                split2v(p1, h[mr][v4 >> 1][2 * (v4 & 1) + 1], l[mr][v4 >> 1][2 * (v4 & 1) + 1]);
+            }
+    };
+    // PIPE (LayerNorm rows into a DMA tile): the A operand runs one chunk ahead of the MFMAs.  A chunk enters with its pieces in registers
+    // (pa: [mr][row half][h 0-3 | l 0-3]) and starts with the weight-fragment reads, as the piece-input kernel does; the rows of the NEXT
+    // chunk (xf, landed) are normalized and split under this chunk's MFMAs — the same arithmetic on the same values, only
+    // elsewhere in the instruction stream.  Chunk 0 of a tile is split here, at the tile's top, with the tile's own LayerNorm constants
+    // (a chained tile hands over raw rows, as before: its row tile, and so its constants, may differ): one exposed split per tile.
+    // Only GS_A_LN (qkv, fc1: the 256 x 256 tile, where it was measured).  The plain f32-row forms (GS_A_F32) keep the split at the
+    // chunk's top: pipelined, their 128 x 128 tile needs 266-282 registers — one workgroup per CU where the plan launches two — and two
+    // 256 x 256 forms nearly double their scratch (profiles/README.md); no forward of many frames runs them.
+    constexpr bool PIPE = !DEEP && AMODE == GS_A_LN;
+    xf_t pa;
+    if constexpr (PIPE) {
+        uint32_t h0[MR][2][4], l0[MR][2][4];
+        split_a(xf, h0, l0);
+#pragma unroll
+        for (int e = 0; e < 16 * MR; ++e) pa[e] = (e & 4 ? l0 : h0)[e >> 4][(e >> 3) & 1][e & 3];
+    }
+    // conv (PIPE): this chunk splits the next one — every chunk of a tile but its last, which runs as a second copy of the body behind
+    // the loop (no branch inside a chunk: the MFMAs and the split are one block for the scheduler)
+    auto chunk_body = [&](const int c, qr_t &q_load, qr_t &q_store, auto conv) __attribute__((always_inline)) {
+        constexpr bool CONV = PIPE && decltype(conv)::value;
         const int buf = (c + par) & 1;
         // this chunk's rows as fp16 pieces — [mr][row half] of 8 halfs (DEEP: [mr][sub-step]) —, then the next chunk's loads go in flight
         uint32_t ah[MR][2][4], al[MR][2][4];
+        if constexpr (PIPE) {
 #pragma unroll
-        for (int mr = 0; mr < MR; ++mr) {
-            if (APIECES) {
+            for (int e = 0; e < 16 * MR; ++e) (e & 4 ? al : ah)[e >> 4][(e >> 3) & 1][e & 3] = pa[e];
+        } else if constexpr (APIECES) {
+#pragma unroll
+            for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     ah[mr][0][e] = xf[16 * mr + e]; ah[mr][1][e] = xf[16 * mr + 4 + e];
                     al[mr][0][e] = xf[16 * mr + 8 + e]; al[mr][1][e] = xf[16 * mr + 12 + e];
                 }
-            } else {
-#pragma unroll
-                for (int v4 = 0; v4 < 4; ++v4) {
-                    // pairs through the packed f32 instructions (v_pk_add_f32 / v_pk_mul_f32): half the vector issue slots
-                    f32x2_t p0 = {__uint_as_float(xf[16 * mr + 4 * v4]), __uint_as_float(xf[16 * mr + 4 * v4 + 1])};
-                    f32x2_t p1 = {__uint_as_float(xf[16 * mr + 4 * v4 + 2]), __uint_as_float(xf[16 * mr + 4 * v4 + 3])};
-                    if constexpr (AMODE == GS_A_LN) {
-                        const int lr = mr * RH + (v4 >> 1) % RH;            // the row the four floats belong to
-                        const f32x2_t mm = {ln_m[lr], ln_m[lr]}, rr = {ln_rs[lr], ln_rs[lr]};
-                        p0 = (p0 - mm) * rr;
-                        p1 = (p1 - mm) * rr;
-                    } else {
-                        const f32x2_t ss = {a_scale, a_scale};
-                        p0 *= ss;
-                        p1 *= ss;
-                    }
-                    split2v(p0, ah[mr][v4 >> 1][2 * (v4 & 1)], al[mr][v4 >> 1][2 * (v4 & 1)]);
-                    split2v(p1, ah[mr][v4 >> 1][2 * (v4 & 1) + 1], al[mr][v4 >> 1][2 * (v4 & 1) + 1]);
-                }
-            }
+        } else {
+            split_a(xf, ah, al);
         }
         xf = xg;
         // ONE load site per operand: the last two chunks request the next tile's first two (a second load site under its own
         // branch made the compiler merge the two results with register copies — and wait for the loads right there)
-        const bool a_next = c + 2 >= nchunks, w_next = c + 1 >= nchunks;
+        const bool a_next = PIPE && !CONV ? true : c + 2 >= nchunks, w_next = PIPE ? !CONV : c + 1 >= nchunks;
         const bool w_req = !w_next || has_next, a_req = !a_next || has_next;    // (DMA schedule) whether there is a chunk to request
         if constexpr (DEEP) {
             // unconditional requests (the last two iterations repeat the last chunk): behind a branch the compiler cannot count on the
@@ -551,14 +579,20 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
             // Issue order of a chunk: the next weight chunk's DMA, then the A loads.  The wait at the chunk's end then leaves exactly the
             // A loads in flight, and the DMAs — older than those — add nothing to the compiler's own count for them.
             if (w_req) dma_w(buf ^ 1, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
-            if (a_req) {
+            // PIPE: the A request is unconditional — where there is no chunk to request (the end of a tile that does not chain) it
+            // repeats the tile's last chunk, in bounds and never used.  Behind a branch the loaded registers and the kept ones meet at a
+            // join: a copy of the set, and a wait for the newest loads right behind the barrier.  Such a request stays outstanding past
+            // the tile's last chunk (into the epilogue, a prologue that does not chain, the kernel's end): nothing behind a tile's last
+            // chunk may rely on xg's contents or on a vm count that assumes these 4 * MR loads have landed or were never issued.
+            if (PIPE || a_req) {
+                const bool far = a_next && a_req;                                // the request goes to the next tile's rows
                 const int64_t nrow0 = next_tm * TROWS + wr * (MR * 32);
                 uint32_t ap[MR][RH];
 #pragma unroll
                 for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
-                    for (int rh = 0; rh < RH; ++rh) ap[mr][rh] = a_next ? row_off(nrow0, mr, rh) : arow[mr][rh];
-                load_a(xg, a_next ? tile_base(nrow0) : abase, ap, a_next ? c + 2 - nchunks : c + 2);
+                    for (int rh = 0; rh < RH; ++rh) ap[mr][rh] = far ? row_off(nrow0, mr, rh) : arow[mr][rh];
+                load_a(xg, far ? tile_base(nrow0) : abase, ap, far ? c + 2 - nchunks : a_next ? nchunks - 1 : c + 2);
             }
         }
         if constexpr (DEEP) {
@@ -629,8 +663,24 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                             acc[mr][rh][b * TB + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[t], *(const half8_t *)ah[mr][rh], acc[mr][rh][b * TB + t], 0, 0, 0);     // h h
             }
         }
+        if constexpr (CONV) {
+            // The next chunk's pieces, from xf: a copy, made at the chunk's top, of rows requested a chunk earlier.  The wait for those
+            // rows stands at the copy (the compiler's vmcnt(0), beside the chunk's DMAs, which it lets pass the copy: it lands them too —
+            // measured harmless; holding the copy in front of the DMAs moved it and its waits behind the last MFMA and was slower,
+            // profiles/README.md), so the split itself waits for no memory operation and leaves this chunk's A loads in flight.  The
+            // split has no operand in common with the MFMAs: the scheduler moves it up among those of the chunk's second half; an MFMA
+            // holds the issue port for 4 of its 16 cycles.  (Pinned one instruction per MFMA with sched_group_barrier, the schedule
+            // needs more registers than the kernel has and the compiler falls back to the order as written: profiles/README.md.)
+            uint32_t nh[MR][2][4], nl[MR][2][4];
+            split_a(xf, nh, nl);
+#pragma unroll
+            for (int e = 0; e < 16 * MR; ++e) pa[e] = (e & 4 ? nl : nh)[e >> 4][(e >> 3) & 1][e & 3];
+        }
         if constexpr (DEEP) {
             if (c + 1 < nchunks) store_w(q_store, buf ^ 1);
+        } else if constexpr (PIPE) {
+            // the DMAs have landed before any wavefront reads the buffer (after the barrier); the A loads — younger — stay in flight
+            gs_wait_vm<4 * MR>();
         } else {
             // the DMAs have landed before any wavefront reads the buffer (after the barrier); the A loads stay in flight
             if (a_req) gs_wait_vm<4 * MR>();
@@ -644,12 +694,15 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
         //  runs its last chunk after the loop.)
         const int even = nchunks & ~1;
         for (int c = 0; c < even; c += 2) {
-            chunk_body(c, qr, qr2);
-            chunk_body(c + 1, qr2, qr);
+            chunk_body(c, qr, qr2, gs_flag<false>());
+            chunk_body(c + 1, qr2, qr, gs_flag<false>());
         }
-        if (nchunks & 1) chunk_body(nchunks - 1, qr, qr2);
+        if (nchunks & 1) chunk_body(nchunks - 1, qr, qr2, gs_flag<false>());
+    } else if (PIPE) {
+        for (int c = 0; c + 1 < nchunks; ++c) chunk_body(c, qr, qr, gs_flag<true>());
+        chunk_body(nchunks - 1, qr, qr, gs_flag<false>());
     } else {
-        for (int c = 0; c < nchunks; ++c) chunk_body(c, qr, qr);
+        for (int c = 0; c < nchunks; ++c) chunk_body(c, qr, qr, gs_flag<false>());
     }
     par = (par + nchunks) & 1;
     GS_T(3);
