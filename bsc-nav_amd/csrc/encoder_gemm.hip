@@ -21,7 +21,10 @@
 //              [32 c + 8 g, + 8) of rows i and i + 16 of its wavefront's 32 (one 128-byte line per row and K chunk over the four
 //              lane groups) and splits them in registers (v_cvt_pk_f16_f32); a uniform base + a 32-bit offset per lane and row;
 //   W operand  pieces precomputed once per weight matrix (bsc_enc_split_weights: planes h, l of (N,K) fp16), one 32-wide K chunk
-//              at a time from global memory straight into LDS (global_load_lds_dwordx4: no register stage), double-buffered;
+//              at a time from global memory straight into LDS (global_load_lds_dwordx4: no register stage) — the 256-row tiles into a
+//              ring of three buffers, chunk c + 2 requested behind the last fragment read of chunk c (off the chunk's top, where all
+//              eight wavefronts stand behind the barrier and wait for their first fragments), the 128 x 128 tile into two, chunk
+//              c + 1 requested at the top of chunk c; one barrier per chunk, at its end, in both;
 //              64-byte rows whose 16-byte columns are XOR-swizzled on the SOURCE address (conflict-free 16-byte reads of 16 rows x
 //              4 columns: gs_w_swz of gemm_split_plan.h, where all lane -> address maps of this loop live);
 //   MFMA       a chunk is ONE K step: per wavefront 16 column tiles of 16 x 2 row halves x 3 products = 96 MFMAs, 32 ds_read_b128.
@@ -48,13 +51,28 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 #ifdef BSC_GEMM_PROFILE        // per-workgroup phase stamps (100 MHz wall clock) + the CU it ran on: -DBSC_GEMM_PROFILE, BSC_GEMM_PROFILE_DUMP=1
 #define GS_PROF_MAX 8192
-__device__ uint64_t g_gemm_prof[GS_PROF_MAX][6];
+#define GS_PROF_COLS 12
+__device__ uint64_t g_gemm_prof[GS_PROF_MAX][GS_PROF_COLS];
 #define GS_T(k)                                                                                                                   \
     do {                                                                                                                          \
         if (threadIdx.x == 0 && prof_idx < GS_PROF_MAX) g_gemm_prof[prof_idx][k] = wall_clock64();                                \
     } while (0)
+// Segments of a chunk of the DMA-scheduled tiles in SHADER cycles (s_memtime), summed over a tile's chunks in scalar registers and
+// stored once behind the loop — columns 6..11: weight-DMA issue, end-of-chunk wait + barrier, barrier -> first MFMA operand back
+// from LDS (holds the DMA issue where that stands at the chunk's top), the whole loop, its chunk count, the end-of-chunk wait alone.
+// A stamp waits for the wavefront's LDS reads (lgkmcnt(0) inside the statement: s_memtime returns out of order with them) and nothing
+// is scheduled across it: read this build's SHARES, not its run time.  A stamp costs about 40 cycles, which every segment holds once.
+#define GS_CYC(t)                                                                                                                 \
+    do {                                                                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                                        \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                                        \
+    } while (0)
+#define GS_CYC_ADD(sum, from, to) ((sum) += (to) - (from))
 #else
 #define GS_T(k)
+#define GS_CYC(t)
+#define GS_CYC_ADD(sum, from, to)
 #endif
 
 __device__ __forceinline__ uint32_t pack_f16_rne(float lo, float hi)        // v_cvt_pk_f16_f32
@@ -308,10 +326,11 @@ __global__ __launch_bounds__(GS_TPB) void k_split_rows(const float *__restrict__
 // (as 2 row halves x 2 NT tiles of 16 where the MFMA is 16x16x32): every weight fragment read from LDS feeds MR * 3 MFMAs per row half.
 // APIECES: A comes as P32 pieces (made by the producing kernel) — otherwise as f32 rows, split in registers.
 // CPIECES: C leaves as P32 pieces scaled by c_scale (the hidden tensor of the MLP: read by the next GEMM only).
-// One tile of a persistent workgroup.  primed: the first two A chunks (xf, xg) and the first weight chunk (LDS buffer `par`) were
-// requested / staged by the tile before, under its last two K chunks; has_next: do the same for the tile (next_tm, next_n0) — of
-// the same shape — so that a workgroup's tiles form one continuous stream of chunks and only its first tile pays the latency of
-// a prologue.  par: parity of the LDS buffer that holds chunk 0 (advances by the chunk count per tile).
+// One tile of a persistent workgroup.  primed: the first two A chunks (xf, xg) and the first weight chunk (LDS buffer `par`; with the
+// ring of three the first two, in `par` and the buffer after it) were requested / staged by the tile before, under its last two K
+// chunks; has_next: do the same for the tile (next_tm, next_n0) — of the same shape — so that a workgroup's tiles form one continuous
+// stream of chunks and only its first tile pays the latency of a prologue.  par: index of the LDS buffer that holds chunk 0 (advances
+// by the chunk count per tile, modulo the number of buffers).
 template <int MR> struct gs_xf { typedef uint32_t type __attribute__((ext_vector_type(16 * MR))); };
 template <bool B> struct gs_flag { static constexpr bool value = B; };
 // AMODE: how the activation operand arrives — GS_A_F32 f32 rows (split in registers), GS_A_PIECES P32 pieces, GS_A_LN f32 rows of
@@ -336,14 +355,16 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     // k_full: the operands' row length (A rows, weight rows); K: the stretch of it this launch contracts (split-K slices of the
     // few-rows path: the kernel wrapper has moved the operand pointers to the slice's first column; otherwise K == k_full)
     constexpr bool APIECES = AMODE == GS_A_PIECES;
-    // the two weight schedules: the few-rows tile (DEEP, below) stages its chunks through registers, two chunks ahead; every other
-    // tile moves them global -> LDS by DMA, one chunk ahead
+    // the weight schedules: the few-rows tile (DEEP, below) stages its chunks through registers, two chunks ahead; every other
+    // tile moves them global -> LDS by DMA — one chunk ahead into two buffers, requested at the chunk's top (the 128 x 128 tile), or
+    // two chunks ahead into a ring of three, requested behind the chunk's last fragment read (RING3: the 256-row tiles; gs_w_ring)
     constexpr bool DEEP = MR == 1 && NT == 1 && WR == 1;
     constexpr int PITCH = DEEP ? GS_PITCH : GS_KC;                            // a DMA's LDS image is lane-linear: no padding
-    constexpr int WROWS = WC * NT * 32;                                       // Ws: [2][2][WROWS][PITCH]
+    constexpr int WROWS = WC * NT * 32;                                       // Ws: [2 or 3][2][WROWS][PITCH]
     constexpr int TROWS = WR * MR * 32;
     constexpr int BUF = 2 * WROWS * PITCH;
     constexpr int NTHR = 64 * WR * WC;
+    constexpr bool RING3 = !DEEP && gs_w_ring(NTHR) == 3;
     constexpr int NLD = 2 * WROWS * 4 / NTHR;                                 // 16-byte pieces of a weight chunk per thread
     // (the wavefront's index as a scalar: its rows, LDS blocks and strips are then scalar arithmetic, not registers per lane)
     // (The thread index goes through an opaque copy per tile: what a tile derives from it per lane — fragment rows, LDS offsets — is a few
@@ -498,6 +519,7 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
             store_w(qr, par);
         } else {
             dma_w(par, n0, 0);
+            if (RING3 && nchunks > 1) dma_w(gs_ring_next(par), n0, 1);            // the ring is primed two chunks deep
             load_a(xf, abase, arow, 0);
             if (nchunks > 1) load_a(xg, abase, arow, 1);
             gs_wait_vm<0>();
@@ -546,9 +568,15 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     }
     // conv (PIPE): this chunk splits the next one — every chunk of a tile but its last, which runs as a second copy of the body behind
     // the loop (no branch inside a chunk: the MFMAs and the split are one block for the scheduler)
+#ifdef BSC_GEMM_PROFILE
+    uint64_t pf_dma = 0, pf_wait = 0, pf_vm = 0, pf_top = 0, pf_a = 0, pf_w = 0, pf_b = 0, pf_c = 0, pf_d = 0, pf_e = 0, pf_loop0 = 0;
+    GS_CYC(pf_e);                                                           // stands for "the far side of the barrier" of chunk 0
+    pf_loop0 = pf_e;
+#endif
+    int ring = par;                                                         // (RING3) par + c mod 3, carried from chunk to chunk
     auto chunk_body = [&](const int c, qr_t &q_load, qr_t &q_store, auto conv) __attribute__((always_inline)) {
         constexpr bool CONV = PIPE && decltype(conv)::value;
-        const int buf = (c + par) & 1;
+        const int buf = RING3 ? ring : (c + par) & 1;                       // the buffer that holds chunk c
         // this chunk's rows as fp16 pieces — [mr][row half] of 8 halfs (DEEP: [mr][sub-step]) —, then the next chunk's loads go in flight
         uint32_t ah[MR][2][4], al[MR][2][4];
         if constexpr (PIPE) {
@@ -568,17 +596,38 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
         xf = xg;
         // ONE load site per operand: the last two chunks request the next tile's first two (a second load site under its own
         // branch made the compiler merge the two results with register copies — and wait for the loads right there)
-        const bool a_next = PIPE && !CONV ? true : c + 2 >= nchunks, w_next = PIPE ? !CONV : c + 1 >= nchunks;
+        // (RING3: the weight chunk requested is c + 2, like the A chunk)
+        const bool a_next = PIPE && !CONV ? true : c + 2 >= nchunks, w_next = RING3 ? a_next : PIPE ? !CONV : c + 1 >= nchunks;
         const bool w_req = !w_next || has_next, a_req = !a_next || has_next;    // (DMA schedule) whether there is a chunk to request
+        // The weight request of a chunk (one site per schedule).  Two buffers: chunk c + 1 into the other buffer, at the chunk's top — that
+        // buffer is free only from the barrier on and the data needs the chunk to land.  RING3: chunk c + 2 — of the next tile where this
+        // one ends — into the buffer that chunk c - 1 was read from, behind this chunk's last fragment read.  (The branch round it ends the
+        // scheduler's block in the middle of the chunk.  Made unconditional — a tile that does not chain repeating its last chunk, as the A
+        // request of PIPE does — the chunk is one block again, in which the scheduler spreads the fragment reads wide: 132 - 232 bytes of
+        // scratch per lane instead of 60 - 92.)
+        auto request_w = [&]() __attribute__((always_inline)) {
+            GS_CYC(pf_a);
+            if constexpr (RING3) {
+                if (w_req) dma_w(gs_ring_prev(buf), w_next ? next_n0 : n0, w_next ? c + 2 - nchunks : c + 2);
+            } else {
+                if (w_req) dma_w(buf ^ 1, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
+            }
+            GS_CYC(pf_b);
+            GS_CYC_ADD(pf_dma, pf_a, pf_b);
+        };
         if constexpr (DEEP) {
             // unconditional requests (the last two iterations repeat the last chunk): behind a branch the compiler cannot count on the
             // younger loads being in flight and makes the LDS stores below wait for everything
             load_a(xg, abase, arow, a_next ? nchunks - 1 : c + 2);
             load_w(q_load, n0, a_next ? nchunks - 1 : c + 2);
         } else {
-            // Issue order of a chunk: the next weight chunk's DMA, then the A loads.  The wait at the chunk's end then leaves exactly the
-            // A loads in flight, and the DMAs — older than those — add nothing to the compiler's own count for them.
-            if (w_req) dma_w(buf ^ 1, w_next ? next_n0 : n0, w_next ? 0 : c + 1);
+            // Issue order of a chunk with two buffers: the next weight chunk's DMA, then the A loads.  The wait at the chunk's end then leaves
+            // exactly the A loads in flight, and the DMAs — older than those — add nothing to the compiler's own count for them.  RING3: the A
+            // loads, then (among the MFMAs) the DMA of chunk c + 2; the wait at the chunk's end leaves both in flight.  The compiler's own
+            // wait for the A rows — a vmcnt(0) behind the barrier, on the loop's back edge, with two buffers as with three — covers this
+            // chunk's DMA as well: it has landed when chunk c + 1 begins, half a chunk after its issue, a chunk before its first read
+            // (profiles/README.md, "a ring of three weight buffers").
+            if constexpr (!RING3) request_w();
             // PIPE: the A request is unconditional — where there is no chunk to request (the end of a tile that does not chain) it
             // repeats the tile's last chunk, in bounds and never used.  Behind a branch the loaded registers and the kept ones meet at a
             // join: a copy of the set, and a wait for the newest loads right behind the barrier.  Such a request stays outstanding past
@@ -638,6 +687,13 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                 half8_t wf[TB];
 #pragma unroll
                 for (int t = 0; t < TB; ++t) wf[t] = *(const half8_t *)(wb + gs_frag_off(WROWS, 0, 1, 0, b * TB + t, 0));
+#ifdef BSC_GEMM_PROFILE
+                if (b == 0) {                                   // the first MFMA's weight operand is back from LDS
+                    asm volatile("" : "+v"(wf[0]));
+                    GS_CYC(pf_c);
+                    GS_CYC_ADD(pf_top, pf_e, pf_c);
+                }
+#endif
 #pragma unroll
                 for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -647,6 +703,10 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
                             acc[mr][rh][b * TB + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[t], *(const half8_t *)ah[mr][rh], acc[mr][rh][b * TB + t], 0, 0, 0);     // h l
 #pragma unroll
                 for (int t = 0; t < TB; ++t) wf[t] = *(const half8_t *)(wb + gs_frag_off(WROWS, 0, 0, 0, b * TB + t, 0));
+                // behind the chunk's last fragment read, in front of its trailing MFMAs: the wavefronts are out of step here and the matrix
+                // pipe has work queued, where at the chunk's top all eight stand behind the barrier and wait for their first fragments
+                if constexpr (RING3)
+                    if (b == 2 * NT / TB - 1) request_w();
 #pragma unroll
                 for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -675,9 +735,20 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
             split_a(xf, nh, nl);
 #pragma unroll
             for (int e = 0; e < 16 * MR; ++e) pa[e] = (e & 4 ? nl : nh)[e >> 4][(e >> 3) & 1][e & 3];
+            // (RING3: the pieces exist HERE, in the block of the chunk's last MFMAs.  The wait below stands under a branch, and what only
+            //  the next chunk uses sinks into the block behind it: the whole split in front of the barrier.)
+            if constexpr (RING3) asm volatile("" : "+v"(pa));
         }
+        GS_CYC(pf_d);
         if constexpr (DEEP) {
             if (c + 1 < nchunks) store_w(q_store, buf ^ 1);
+        } else if constexpr (RING3) {
+            // The DMA of chunk c + 1 — requested a chunk ago — has landed before any wavefront reads its buffer (after the barrier); this
+            // chunk's A loads and its DMA (chunk c + 2), both younger, stay in flight.  The count holds only where both were issued: a_req
+            // and w_req are one condition here (and PIPE always issues the A loads); a tile's last two chunks, where it does not chain,
+            // request nothing and wait for everything.
+            if (w_req) gs_wait_vm<4 * MR + NLD>();
+            else gs_wait_vm<0>();
         } else if constexpr (PIPE) {
             // the DMAs have landed before any wavefront reads the buffer (after the barrier); the A loads — younger — stay in flight
             gs_wait_vm<4 * MR>();
@@ -686,7 +757,12 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
             if (a_req) gs_wait_vm<4 * MR>();
             else gs_wait_vm<0>();
         }
+        GS_CYC(pf_w);
+        GS_CYC_ADD(pf_vm, pf_d, pf_w);
         __syncthreads();
+        GS_CYC(pf_e);
+        GS_CYC_ADD(pf_wait, pf_d, pf_e);
+        if constexpr (RING3) ring = gs_ring_next(ring);
     };
     if (DEEP) {
         // (two iterations per trip, no branch between them: a conditional second half made the compiler merge the register sets with
@@ -704,8 +780,14 @@ __device__ __forceinline__ void gemm_split_tile(uint16_t *Ws, char *epi_lds, con
     } else {
         for (int c = 0; c < nchunks; ++c) chunk_body(c, qr, qr, gs_flag<false>());
     }
-    par = (par + nchunks) & 1;
+    par = RING3 ? ring : (par + nchunks) & 1;
     GS_T(3);
+#ifdef BSC_GEMM_PROFILE
+    if (threadIdx.x == 0 && prof_idx < GS_PROF_MAX) {
+        g_gemm_prof[prof_idx][6] = pf_dma; g_gemm_prof[prof_idx][7] = pf_wait; g_gemm_prof[prof_idx][8] = pf_top;
+        g_gemm_prof[prof_idx][9] = pf_e - pf_loop0; g_gemm_prof[prof_idx][10] = (uint64_t)nchunks; g_gemm_prof[prof_idx][11] = pf_vm;
+    }
+#endif
     // The weights are the MFMA's FIRST operand (D' = W X^T): a lane holds ROWS of C and four consecutive columns per register quad.
     // DMA tiles: lane (i, g) of accumulator tile (mr, row half, t') holds row row0 + 32 mr + gs_acc_row and the columns gs_acc_col =
     // 16 t' + 4 g + (0..3) of the wavefront's strip; the quad q = 2 row half + (t' & 1) of the 32-column tile t = t' >> 1 below.
@@ -1284,13 +1366,15 @@ extern "C" bsc_status bsc_enc_gemm_split_ws(const void *a_dev, int64_t M, int32_
     BSC_HIP(hipGetLastError());
 #ifdef BSC_GEMM_PROFILE
     if (getenv("BSC_GEMM_PROFILE_DUMP")) {
-        static uint64_t host[GS_PROF_MAX][6];
+        static uint64_t host[GS_PROF_MAX][GS_PROF_COLS];
         BSC_HIP(hipStreamSynchronize(s));
         BSC_HIP(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_prof), sizeof(host)));
         const int64_t n = p.q_virtual * 8 < GS_PROF_MAX ? p.q_virtual * 8 : GS_PROF_MAX;
-        for (int64_t w = 0; w < n; ++w)
-            fprintf(stderr, "GP %lld %llx %llu %llu %llu %llu %llu\n", (long long)w, (unsigned long long)host[w][0], (unsigned long long)host[w][1],
-                    (unsigned long long)host[w][2], (unsigned long long)host[w][3], (unsigned long long)host[w][4], (unsigned long long)host[w][5]);
+        for (int64_t w = 0; w < n; ++w) {
+            fprintf(stderr, "GP %lld %llx", (long long)w, (unsigned long long)host[w][0]);
+            for (int k = 1; k < GS_PROF_COLS; ++k) fprintf(stderr, " %llu", (unsigned long long)host[w][k]);
+            fprintf(stderr, "\n");
+        }
     }
 #endif
     return BSC_OK;

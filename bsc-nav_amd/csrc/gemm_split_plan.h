@@ -61,12 +61,24 @@ GS_HD GsTile gs_tile_of(int n_tiles_n, int64_t n_tiles_m, int64_t q_full, int64_
 // eight k of rows i and i + 16 of the wavefront's 32, and of the accumulator tile (row half, tile) ROW 16 half + i of C and the four
 // consecutive columns 16 tile + 4 g + (0..3).  tests/host/gemm_frag_main.cpp composes these maps on the CPU; the kernel calls them.
 //
-// The image of a chunk: [2 buffers][2 pieces][wrows rows][4 columns of 16 bytes].  A DMA instruction of a wavefront lands in lane
+// The image: [gs_w_ring buffers][2 pieces][wrows rows][4 columns of 16 bytes], one chunk per buffer (buf = 0 .. gs_w_ring - 1 in
+// gs_dma_lds_off / gs_frag_off; chunk c of a tile sits in buffer (first + c) % gs_w_ring).  A DMA instruction of a wavefront lands in lane
 // order (16 rows x 64 bytes), so the swizzle is applied to the SOURCE column: slot (row, c) holds global column c ^ gs_w_swz(row).
 // A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32): four blocks
 // of four rows, two of them at g and two at g + 1.  A 256-byte bank window is four rows, so the four blocks must sit in four different
 // columns: with q = (row >> 2) & 3 the groups hold {q 0, 3 at g; q 1, 2 at g ^ 1} or {q 1, 2 at g; q 0, 3 at g ^ 1}, and
 // s = {0, 3, 2, 1} separates both (the plain s = q of the 32-row fragment of v_mfma_f32_32x32x16 does not: 0 ^ s[0] = 1 ^ s[1]).
+//
+// Weight buffers of a workgroup of nthr threads.  The 256-row tiles (512 threads, one workgroup per CU; whole and half width) keep a
+// ring of THREE: the buffer of chunk c + 2 was last read in chunk c - 1, whose closing barrier every wavefront has passed, so chunk
+// c may request c + 2 anywhere — the kernel does it behind its last fragment read, off the chunk's top where all eight wavefronts
+// wait for their first fragments — and the request has all of chunk c + 1 to land.  The 128 x 128 tile keeps two (requested at the
+// chunk's top, one ahead): a third would put it at 81 KB with the bias row of N = 4096, one workgroup per CU where the plan launches
+// two.  (The few-rows tile stages through registers into two buffers of its own pitch.)
+GS_HD constexpr int gs_w_ring(int nthr) { return nthr == 512 ? 3 : 2; }
+// the ring of three: the buffer of the chunk after the one in buf, and of the chunk before it — where the chunk two ahead goes
+GS_HD constexpr int gs_ring_next(int buf) { return buf == 2 ? 0 : buf + 1; }
+GS_HD constexpr int gs_ring_prev(int buf) { return buf == 0 ? 2 : buf - 1; }
 GS_HD constexpr int gs_w_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
 GS_HD constexpr int gs_w_col(int row, int c) { return c ^ gs_w_swz(row); }         // slot -> global column and back (an involution)
 // DMA plan of a workgroup of nthr threads for a chunk of wrows rows per piece: instruction j of thread tid moves 16 bytes
@@ -140,7 +152,9 @@ inline bool gs_plan(int64_t M, int K, int N, int epilogue, int a_mode, bool c_pi
     p.q_full = (p.tile == 1 && q_rem > 0 && 2 * q_rem <= p.per_round && q_all > p.per_round) ? q_all - q_rem : q_all;
     p.q_virtual = p.q_full + 2 * (q_all - p.q_full);
     p.n_wg = (p.q_virtual < p.per_round ? p.q_virtual : p.per_round) * 8;
-    p.lds_loop = (int64_t)2 * 2 * p.cols * (p.tile == 6 ? GS_PITCH : GS_KC) * 2;     // [2 buffers][2 pieces][cols][pitch] fp16
+    // [buffers][2 pieces][cols][pitch] fp16: three buffers of 32 KB for the 256 x 256 tile (with 34 KB of epilogue blocks and at most
+    // 16 KB of bias row 146 KB), two for the others
+    p.lds_loop = (int64_t)gs_w_ring(p.threads) * 2 * p.cols * (p.tile == 6 ? GS_PITCH : GS_KC) * 2;
     p.lds_epi = (int64_t)(p.threads / 64) * (32 * 136);            // the epilogue's per-wavefront tile blocks
     p.lds = p.lds_loop + p.lds_epi + p.n_pad * 4;                   // + the bias row
     if (p.lds > GS_LDS_MAX) { *why = "bsc_enc_gemm_split: N does not fit the kernel's LDS plan (bias row)"; return false; }

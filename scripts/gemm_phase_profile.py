@@ -8,8 +8,17 @@ for line in open(sys.argv[1]):
     f = line.split()
     w = int(f[1])
     if w == 0: rows = []
-    rows.append((w, int(f[2], 16)) + tuple(int(v) for v in f[3:8]))
+    rows.append((w, int(f[2], 16)) + tuple(int(v) for v in f[3:8]) + tuple(int(v) for v in f[8:14]))
 rows = [r for r in rows if r[2] != 0]
+# chunk-loop segments (shader cycles, summed over a tile's chunks): medians per chunk over the tiles, and the clock the loop held
+seg = [r for r in rows if len(r) == 13 and r[11] > 0 and r[4] > r[3]]
+if seg:
+    def pc(k): return st.median(r[k] / r[11] for r in seg)
+    dma, wait, top, loop, vm = pc(7), pc(8), pc(9), pc(10), pc(12)
+    ghz = st.median(r[10] / ((r[4] - r[3]) * 10.0) for r in seg)        # cycles per ns; a tick of the wall stamps is 10 ns
+    print(f"per chunk, cycles (median of {len(seg)} tiles, {seg[0][11]} chunks; clock {ghz:.2f} GHz): chunk {loop:.0f} | DMA issue {dma:.0f} ({100 * dma / loop:.1f} %)"
+          f" | wait + barrier {wait:.0f} ({100 * wait / loop:.1f} %; the wait alone {vm:.0f}) | barrier -> first MFMA operand {top:.0f} ({100 * top / loop:.1f} %)"
+          f" | remainder {loop - dma - wait - top:.0f} / {loop - wait - top:.0f} (DMA issue outside / inside barrier -> first MFMA)")
 t0 = min(r[2] for r in rows)
 end = max(r[6] for r in rows)
 print(f"workgroups that ran {len(rows)}, kernel span {(end - t0) / 100:.1f} us")
